@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- GAOT training throughput on MI355X (contract: see the task statement).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" = one reference-trainer step (forward + MSE + backward + AdamW, plus the flat-gradient RCCL all-reduce
@@ -17,7 +17,12 @@ piece products).  Its error against the float64 oracle is in `rel_l2_vs_oracle.v
 Other arithmetic is reported as labelled `variants` (bf16x3: the three-piece products everywhere, equally fp32-level; bf16x2: two
 rounded bf16 pieces, 16 bits; bf16: one piece in the tile GEMMs), each with its own error against the float64 oracle.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the headline line; `--dump-outputs DIR` also writes what the last timed
+step computed (DIR/loss.npy, params.npy, grads.npy, float32; same arguments = same inputs, so two builds compare output for output).
+Everything else -- the roofline blocks, `sustained`, `comm`, `configs`, `reference_loop`, `cpu_baseline` and the oracle comparison,
+`torch_gpu_baseline`, `variants` -- is measured after the headline, only with `--full`.
+
+Extra objects on the JSON line with --full:
   roofline     dominant kernel family = the split-bf16 MFMA GEMM kernels behind gaot_gemm_f32 and the grouped weight-gradient
                launch: piece-product FLOPs ISSUED on the bf16 matrix pipe in one step / their summed duration, timed live with HIP
                events on the launch stream in an instrumented eager step; peak = 2500 TFLOP/s (dense bf16 MFMA, MI355X_MICROARCH.md);
@@ -690,6 +695,70 @@ def hip_reference_pass(ts, model, tensors):
     return out
 
 
+def roofline_blocks(roof, model, dtype):
+    """the `roofline` (matrix pipe) and `roofline_hbm` (fused integral transforms) objects of the line from gemm_roofline()'s event timings"""
+    from gaot_amd import ops as _ops
+    traffic, traffic_src = recorded_traffic("gemm")
+    # HBM regime (SURVEY 8d): the four fused integral-transform kernels of one step.  Algorithmic bytes = every operand
+    # of a launch touched once (k_e rows, node features, CSR arrays, outputs) -- fewer than SURVEY 8d's 42 MB per train
+    # sample because the lifted [B,N,C] tensor and the [B,Nq,C] transform output no longer exist.
+    enc_nb = list(model.encoder.neighbor_cache.values())[0][0]
+    dec_nb = list(model.decoder.neighbor_cache.values())[0][0]
+    Ee, Ed = int(enc_nb["neighbors_index"].numel()), int(dec_nb["neighbors_index"].numel())
+    Q, C, B_ = LATENT[0] * LATENT[1], C_LIFT, BATCH
+    gno_bytes = {
+        "encoder fwd": 4.0 * (Ee * C + B_ * N_NODES * 1 + 3 * Ee + Q + B_ * Q * C),
+        "encoder bwd": 4.0 * (B_ * Q * C + Ee * C + B_ * N_NODES * 1 + 3 * Ee + Ee * C),
+        "decoder fwd": 4.0 * (Ed * C + B_ * Q * C + 3 * Ed + N_NODES + B_ * N_NODES * 1),
+        "decoder bwd": 4.0 * (B_ * N_NODES * 1 + Ed * C + B_ * Q * C + 5 * Ed + Ed * C + B_ * Q * C),
+    }
+    gno_rows = {k: {"us": roof["gno_us"].get(k), "algorithmic_MB": gno_bytes[k] / 1e6,
+                    "GBps": (gno_bytes[k] / (roof["gno_us"][k] * 1e-6) / 1e9) if roof["gno_us"].get(k) else None} for k in gno_bytes}
+    gno_total_us = sum(v for k, v in roof["gno_us"].items() if k in gno_bytes)
+    gno_total_b = sum(gno_bytes.values())
+    hbm_achieved = gno_total_b / (gno_total_us * 1e-6) / 1e9 if gno_total_us > 0 else 0.0
+    gno_traffic, gno_src = recorded_traffic("gno")
+    roofline = {"bound": "mfma", "pipe": "f16 / bf16 mfma (v_mfma_f32_32x32x16_f16 / _bf16: the same 2.5 PFLOP/s dense rate)",
+                "kernel": "every launch of one step on the bf16 matrix pipe behind gaot_gemm_f32: gemm_split_kernel / gemm_ad_kernel (NT / NN tiles: operands staged through registers / both by LDS DMA) and the grouped "
+                          "weight-gradient launch gemm_tn_grouped_kernel; each f32 operand as "
+                          f"{ {'f32': 'two fp16 pieces of the power-of-two scaled operand (24 significant bits up to its last one), three piece products on v_mfma_f32_32x32x16_f16' if _ops._F16_PIECES[0] else 'three exact bf16 pieces, six piece products', 'bf16x2': 'two rounded bf16 pieces, three piece products', 'bf16': 'one bf16 piece, one product'}[dtype] }",
+                "achieved": roof["tflops"], "peak": PEAK_BF16_MATRIX_TFLOPS, "unit": "TFLOP/s",
+                "frac": roof["tflops"] / PEAK_BF16_MATRIX_TFLOPS,
+                "achieved_note": "ALGORITHMIC FLOPs (2MNK per product, each counted once whatever the number of piece products) / event-timed "
+                                 "duration of the family's launches, against the dense f16 / bf16 matrix peak the kernels run on; the pipe "
+                                 "itself is issued three piece products per product: `issued_piece_tflops`",
+                "issued_piece_tflops": roof["piece_tflops"], "issued_frac": roof["piece_tflops"] / PEAK_BF16_MATRIX_TFLOPS,
+                "f32_equivalent_frac_of_f32_matrix_peak": roof["tflops"] / PEAK_F32_MATRIX_TFLOPS,
+                "traffic": traffic,
+                "traffic_note": "HBM bytes per launch, PMC FETCH_SIZE(x2, gfx950)+WRITE_SIZE, separate --pmc passes over the same "
+                                f"launches (eager step): {traffic_src}",
+                "algorithmic_bytes_per_launch": roof["alg_bytes_per_launch"],
+                "launches_per_step": roof["launches"], "gflop_per_step": roof["flops"] / 1e9, "piece_gflop_per_step": roof["piece_flops"] / 1e9,
+                "kernel_ms_per_step": roof["ms"], "avg_launch_us": 1e3 * roof["ms"] / max(1, roof["launches"]),
+                "f32_mfma_tiles": {"launches_per_step": roof["f32_mfma_launches"], "ms_per_step": roof["f32_mfma_ms"], "gflop_per_step": roof["f32_mfma_gflop"],
+                                   "note": "products too small / narrow for the split tiles run on v_mfma_f32_32x32x2_f32 (157.3 TFLOP/s dense): not part of `achieved`"},
+                "skinny_valu_launches_per_step": roof["skinny_launches"], "all_gemm_entry_ms_per_step": roof["all_gemm_ms"]}
+    roofline_hbm = {"bound": "hbm", "kernel": "fused integral-transform kernels of one step (csrc/gno.hip, gno_ep.hip): lift_gather_reduce, "
+                                               "lift_edge_grad, proj_fwd_bin, proj_edge_grad + proj_gather_t (row-parallel forms: the bench "
+                                               "mesh is not degree-skewed; skewed plans take the edge-partitioned forms)",
+                    "achieved": hbm_achieved, "peak": PEAK_HBM_GBPS, "unit": "GB/s", "frac": hbm_achieved / PEAK_HBM_GBPS,
+                    "traffic": gno_traffic, "traffic_note": f"HBM bytes of the family per step, PMC FETCH_SIZE(x2)+WRITE_SIZE: {gno_src}",
+                    "algorithmic_bytes_per_step": gno_total_b, "kernel_us_per_step": gno_total_us, "per_kernel": gno_rows,
+                    "edges": {"encoder": Ee, "decoder": Ed}}
+    return roofline, roofline_hbm
+
+
+def dump_outputs(path: str, ts, loss) -> None:
+    """what the last timed step handed its caller, as float32 `path`/<name>.npy: `loss` (the tensor TrainStep.step() returns), `params`
+    (the flat parameter buffer after that step's update) and `grads` (the flat gradient buffer it was computed from); 2 x 13.6 MB"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    params = ts.opt.flat_p if hasattr(ts.opt, "flat_p") else torch.cat([q.detach().reshape(-1) for q in ts.bucket.params])
+    for name, v in (("loss", loss.reshape(1)), ("params", params), ("grads", ts.bucket.flat)):
+        np.save(os.path.join(path, name + ".npy"), v.detach().float().cpu().numpy())
+
+
 def self_launch(n: int) -> None:
     """re-run this command line under `python -m torch.distributed.run --nnodes=1 --nproc-per-node n` on a free loopback port and pass
     its stdout / exit status through (stderr of the ranks goes to ours)"""
@@ -722,6 +791,12 @@ def main():
                          "line at that narrower arithmetic (A/B and profiling runs; the line says so in `dtype`).  The default line "
                          "already carries both as `variants`.")
     ap.add_argument("--no-variants", action="store_true", help="skip the bf16x2 / bf16 variant measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else the line can carry: the roofline blocks, `sustained`, `comm` "
+                         "(N > 1), `configs`, `reference_loop`, `cpu_baseline`, `rel_l2_vs_oracle`, `torch_gpu_baseline`, `variants` (the --no-* "
+                         "options trim this set).  Without it a run sets up, warms up, times the steps and prints the headline.")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32): loss, params, grads")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -757,7 +832,7 @@ def main():
     torch.manual_seed(0)                      # identical weights on every rank (and broadcast from rank 0 anyway)
     model = build_model().to(dev).train()
     lat, x, p, t = synthetic(1234 + rank, dev)
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     sd0 = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()} if want_cpu else None
     staged = {"0": False, "1": True}.get(os.environ.get("GAOT_BENCH_STAGED", ""), None)     # A/B hook; default: staged when world > 1
     ts = TrainStep(model, lr=8e-4, weight_decay=1e-5, use_graph=not args.no_graph, staged=staged)
@@ -774,10 +849,13 @@ def main():
         ts.step()
     sync()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        ts.step()
+        last = ts.step()
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ts, last)
     if world > 1:
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -785,7 +863,7 @@ def main():
     loss = float(ts._loss if ts.use_graph else ts.step())
     comm = None
     ranks_seen = None
-    if world > 1:
+    if world > 1 and args.full:
         # proof that the collective saw N distinct ranks / devices and that they stayed identical: every rank contributes its device index
         # and a checksum of its flat parameter buffer after the timed steps (one all-gather, after the timed region)
         flat_w = ts.opt.flat_p if hasattr(ts.opt, "flat_p") else torch.cat([q.detach().reshape(-1) for q in model.parameters()])
@@ -832,30 +910,10 @@ def main():
                         "(ReduceOp.AVG) of its slice of the flat gradient buffer, issued while the next group's backward graph replays; exposed = "
                         "headline step - the same step without the exchange"}
 
-    roof = gemm_roofline(ts)
+    roof = gemm_roofline(ts) if args.full else None
     if rank == 0:
         n_params = sum(q.numel() for q in model.parameters())
         ms_step = 1e3 * elapsed / args.steps
-        traffic, traffic_src = recorded_traffic("gemm")
-        # HBM regime: the four fused integral-transform kernels of one step.  Algorithmic bytes = every operand
-        # of a launch touched once (k_e rows, node features, CSR arrays, outputs) -- fewer than SURVEY 8d's 42 MB per train
-        # sample because the lifted [B,N,C] tensor and the [B,Nq,C] transform output no longer exist.
-        enc_nb = list(model.encoder.neighbor_cache.values())[0][0]
-        dec_nb = list(model.decoder.neighbor_cache.values())[0][0]
-        Ee, Ed = int(enc_nb["neighbors_index"].numel()), int(dec_nb["neighbors_index"].numel())
-        Q, C, B_ = LATENT[0] * LATENT[1], C_LIFT, BATCH
-        gno_bytes = {
-            "encoder fwd": 4.0 * (Ee * C + B_ * N_NODES * 1 + 3 * Ee + Q + B_ * Q * C),
-            "encoder bwd": 4.0 * (B_ * Q * C + Ee * C + B_ * N_NODES * 1 + 3 * Ee + Ee * C),
-            "decoder fwd": 4.0 * (Ed * C + B_ * Q * C + 3 * Ed + N_NODES + B_ * N_NODES * 1),
-            "decoder bwd": 4.0 * (B_ * N_NODES * 1 + Ed * C + B_ * Q * C + 5 * Ed + Ed * C + B_ * Q * C),
-        }
-        gno_rows = {k: {"us": roof["gno_us"].get(k), "algorithmic_MB": gno_bytes[k] / 1e6,
-                        "GBps": (gno_bytes[k] / (roof["gno_us"][k] * 1e-6) / 1e9) if roof["gno_us"].get(k) else None} for k in gno_bytes}
-        gno_total_us = sum(v for k, v in roof["gno_us"].items() if k in gno_bytes)
-        gno_total_b = sum(gno_bytes.values())
-        hbm_achieved = gno_total_b / (gno_total_us * 1e-6) / 1e9 if gno_total_us > 0 else 0.0
-        gno_traffic, gno_src = recorded_traffic("gno")
         n_prod = {"f32": 3.0 if _ops._F16_PIECES[0] else 6.0, "bf16x2": 3.0, "bf16": 1.0}[args.dtype]
         t_mfma_ideal = n_prod * 259.0e9 / (PEAK_BF16_MATRIX_TFLOPS * 1e12) * 1e3   # 259 GFLOP per B = 8 step, as piece products on the pipe in use
         t_hbm_ideal = (8 * (42 + 120) + 13) * 1e6 / (PEAK_HBM_GBPS * 1e9) * 1e3   # ~1.31 GB per step
@@ -891,41 +949,17 @@ def main():
                        "h2d": "excluded: the timed region replays one batch bound in HBM ahead of time (TrainStep.bind); nothing is uploaded or "
                               "re-copied per step (the PCIe-inclusive drop-in rate is `reference_loop`)",
                        "hipgraph": ts.use_graph, "staged_backward_phases": ts.bucket.n_phases, "stage_groups": ts.stage_groups, "final_loss": loss},
-            "roofline": {"bound": "mfma", "pipe": "f16 / bf16 mfma (v_mfma_f32_32x32x16_f16 / _bf16: the same 2.5 PFLOP/s dense rate)",
-                         "kernel": "every launch of one step on the bf16 matrix pipe behind gaot_gemm_f32: gemm_split_kernel / gemm_ad_kernel (NT / NN tiles: operands staged through registers / both by LDS DMA) and the grouped "
-                                   "weight-gradient launch gemm_tn_grouped_kernel; each f32 operand as "
-                                   f"{ {'f32': 'two fp16 pieces of the power-of-two scaled operand (24 significant bits up to its last one), three piece products on v_mfma_f32_32x32x16_f16' if _ops._F16_PIECES[0] else 'three exact bf16 pieces, six piece products', 'bf16x2': 'two rounded bf16 pieces, three piece products', 'bf16': 'one bf16 piece, one product'}[args.dtype] }",
-                         "achieved": roof["tflops"], "peak": PEAK_BF16_MATRIX_TFLOPS, "unit": "TFLOP/s",
-                         "frac": roof["tflops"] / PEAK_BF16_MATRIX_TFLOPS,
-                         "achieved_note": "ALGORITHMIC FLOPs (2MNK per product, each counted once whatever the number of piece products) / event-timed "
-                                          "duration of the family's launches, against the dense f16 / bf16 matrix peak the kernels run on; the pipe "
-                                          "itself is issued three piece products per product: `issued_piece_tflops`",
-                         "issued_piece_tflops": roof["piece_tflops"], "issued_frac": roof["piece_tflops"] / PEAK_BF16_MATRIX_TFLOPS,
-                         "f32_equivalent_frac_of_f32_matrix_peak": roof["tflops"] / PEAK_F32_MATRIX_TFLOPS,
-                         "traffic": traffic,
-                         "traffic_note": "HBM bytes per launch, PMC FETCH_SIZE(x2, gfx950)+WRITE_SIZE, separate --pmc passes over the same "
-                                         f"launches (eager step): {traffic_src}",
-                         "algorithmic_bytes_per_launch": roof["alg_bytes_per_launch"],
-                         "launches_per_step": roof["launches"], "gflop_per_step": roof["flops"] / 1e9, "piece_gflop_per_step": roof["piece_flops"] / 1e9,
-                         "kernel_ms_per_step": roof["ms"], "avg_launch_us": 1e3 * roof["ms"] / max(1, roof["launches"]),
-                         "f32_mfma_tiles": {"launches_per_step": roof["f32_mfma_launches"], "ms_per_step": roof["f32_mfma_ms"], "gflop_per_step": roof["f32_mfma_gflop"],
-                                            "note": "products too small / narrow for the split tiles run on v_mfma_f32_32x32x2_f32 (157.3 TFLOP/s dense): not part of `achieved`"},
-                         "skinny_valu_launches_per_step": roof["skinny_launches"], "all_gemm_entry_ms_per_step": roof["all_gemm_ms"]},
-            "roofline_hbm": {"bound": "hbm", "kernel": "fused integral-transform kernels of one step (csrc/gno.hip, gno_ep.hip): lift_gather_reduce, "
-                                                        "lift_edge_grad, proj_fwd_bin, proj_edge_grad + proj_gather_t (row-parallel forms: the bench "
-                                                        "mesh is not degree-skewed; skewed plans take the edge-partitioned forms)",
-                             "achieved": hbm_achieved, "peak": PEAK_HBM_GBPS, "unit": "GB/s", "frac": hbm_achieved / PEAK_HBM_GBPS,
-                             "traffic": gno_traffic, "traffic_note": f"HBM bytes of the family per step, PMC FETCH_SIZE(x2)+WRITE_SIZE: {gno_src}",
-                             "algorithmic_bytes_per_step": gno_total_b, "kernel_us_per_step": gno_total_us, "per_kernel": gno_rows,
-                             "edges": {"encoder": Ee, "decoder": Ed}},
             "roofline_step": {"t_mfma_ideal_ms": t_mfma_ideal, "t_hbm_ideal_ms": t_hbm_ideal,
                               "achieved": max(t_mfma_ideal, t_hbm_ideal) / ms_step,
                               "note": "SURVEY 8d: max(t_HBM, t_MFMA)_ideal / t_measured with 259 GFLOP (x piece products per product, on the bf16 "
                                       "matrix pipe at 2500 TFLOP/s) and ~1.31 GB of algorithmic work per 8-sample step at 8 TB/s"},
         }
+        if roof is not None:
+            line["roofline"], line["roofline_hbm"] = roofline_blocks(roof, model, args.dtype)
         if comm is not None:
             line["comm"] = comm
-        if world == 1:
+        one_full = world == 1 and args.full          # everything below: further measurements and checks, after the headline
+        if one_full:
             # sustained figure: the same step for at least one second of wall time (the headline window is K steps ~ 0.15 s)
             n_sus = max(args.steps, int(1.2 / max(ms_step * 1e-3, 1e-6)))
             torch.cuda.synchronize()
@@ -936,10 +970,10 @@ def main():
             dt_sus = time.perf_counter() - t0
             line["sustained"] = {"value": BATCH * n_sus / dt_sus, "unit": "samples/s", "steps": n_sus, "seconds": dt_sus,
                                  "ms_per_step": 1e3 * dt_sus / n_sus}
-        if world == 1 and not args.no_configs:
+        if one_full and not args.no_configs:
             del ts
             line["configs"] = secondary_configs(dev, oracle=not args.no_cpu_baseline)
-        if world == 1 and not args.no_reference_loop:
+        if one_full and not args.no_reference_loop:
             line["reference_loop"] = reference_loop_rate(dev)
             line["reference_loop"]["frac_of_headline"] = line["reference_loop"]["value"] / line["value"]
         ref64 = None
@@ -951,7 +985,7 @@ def main():
             except Exception as e:          # a baseline leg must never cost the line
                 line["torch_gpu_baseline"] = {"error": f"{type(e).__name__}: {e}"[:300]}
             torch.cuda.empty_cache()
-        if world == 1 and not args.no_variants and args.dtype == "f32":
+        if one_full and not args.no_variants and args.dtype == "f32":
             # narrower arithmetic than the reference's fp32: labelled variants next to the headline, each with its own error vs float64
             line["variants"] = {nm: variant_rate(dev, nm, ref64) for nm in ("bf16x3", "bf16x2", "bf16")}
             for v in line["variants"].values():
