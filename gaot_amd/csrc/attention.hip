@@ -11,64 +11,9 @@
 // Reduction order inside a tile is free, so k-slots are chosen to make every LDS read conflict-free
 // (ds_read_b128 on +4-padded rows for A operands, row-contiguous ds_read_b32 otherwise).
 // Everything is deterministic: no atomics; dQ partials per key block are reduced in a fixed order.
-#include "common.h"
+#include "attention_common.h"
 
 namespace gaot {
-
-constexpr float LOG2E = 1.4426950408889634f;
-
-struct AttnArgs {
-    const float *q, *k, *v;
-    long ldq, ldk, ldv;
-    int B, S, H, Hkv, D;
-    float* o; long ldo; float* lse;
-    // backward
-    const float *oin, *dout; float *dq, *dk, *dv; long lddq, lddk, lddv;
-    float* delta; float* dq_part; int n_kblocks;
-    float *dk2, *dv2;          // query-split backward (QS = 2): dense [B S][H 32] partials of the second half of the query tiles
-    float *o_part, *lse_part;  // key-split forward (KS = 2): per half the normalised output [B S][H D] (dense) and its log-sum-exp [B H S]
-    float scale; int vec;
-    // attention dropout (attn.py:110-114, dropout_p of F.scaled_dot_product_attention in training): P is multiplied by
-    // keep(b, h, q, k) / (1 - p) after the softmax; the mask is a counter-based hash of (*drop_seed, element index), so the
-    // backward regenerates it from the same seed word
-    const unsigned long long* drop_seed; unsigned drop_thresh; float drop_scale;
-    // fp16-piece kernels (pieces = 4): magnitude words of the q | k | v operands (one word: they are one tensor) and of dO
-    const float* qkv_amax; const float* dout_amax;
-    float* dqkv_amax;          // optional: published magnitude word of dq | dk | dv
-};
-
-// splitmix64 finaliser of (seed + linear index of the score): the top 32 bits against the keep threshold
-__device__ __forceinline__ float attn_drop_factor(unsigned long long seed, long idx, unsigned thresh, float scale) {
-    unsigned long long x = seed + (unsigned long long)idx;
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27; x *= 0x94d049bb133111ebull;
-    x ^= x >> 31;
-    return (unsigned)(x >> 32) < thresh ? scale : 0.f;
-}
-
-// id -> (group, member): groups are dealt to XCDs round-robin, all members of a group stay on the group's XCD.
-// With G groups of n members: XCD x = id % 8 serves groups x, x+8, ...; falls back to the plain order when G % 8 != 0.
-__device__ __forceinline__ void xcd_group_decode(int id, int G, int n, int& group, int& member) {
-    if ((G & 7) == 0) {
-        const int x = id & 7, t = id >> 3;        // t-th workgroup on XCD x
-        group = x + 8 * (t / n);
-        member = t % n;
-    } else {
-        group = id / n;
-        member = id % n;
-    }
-}
-
-__device__ __forceinline__ f32x4 load4(const float* __restrict__ row, int d, int D, bool row_ok, bool vec) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (!row_ok) return v;
-    if (vec) { if (d < D) v = *reinterpret_cast<const f32x4*>(row + d); }
-    else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) if (d + j < D) v[j] = row[d + j];
-    }
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------------
 // forward: workgroup = 4 waves x 32 queries; key/value tiles of 64 rows staged through LDS
@@ -2947,10 +2892,15 @@ extern "C" int gaot_attention_fwd_ws(const float* q, const float* k, const float
     const int g_attn_pp = ::g_attn_pp >= 0 ? ::g_attn_pp : (pieces == 2 ? 22 : 33);
     const int g_attn_op = ::g_attn_op >= 0 ? ::g_attn_op : (pieces == 2 ? 2 : 3);
     GAOT_REQUIRE(B > 0 && S > 0 && H > 0 && Hkv > 0 && H % Hkv == 0, "attention_fwd: bad sizes B=%d S=%d H=%d Hkv=%d", B, S, H, Hkv);
-    GAOT_REQUIRE(head_dim > 0 && head_dim <= 128, "attention_fwd: head_dim %d not in 1..128", head_dim);
+    GAOT_REQUIRE(head_dim > 0 && head_dim <= 256, "attention_fwd: head_dim %d not in 1..256", head_dim);
     AttnArgs a = {};
     fill_common(a, q, k, v, ldq, ldk, ldv, B, S, H, Hkv, head_dim);
     a.o = o; a.ldo = ldo; a.lse = lse; a.qkv_amax = qkv_absmax;
+    if (head_dim > 128) {        // 128 < head_dim <= 256: fp32 MFMA with the head dimension split over the waves (attention_wide.hip)
+        attn_wide_fwd_launch(a, false, ST(stream));
+        GAOT_CHECK_LAUNCH("gaot_attention_fwd");
+        return GAOT_OK;
+    }
     dim3 grid(cdiv(S, 128) * B * H), block(256);
     if (workspace != nullptr && f16 && a.vec && aligned16(workspace) && aligned16(o) && ldo % 4 == 0 && fwd_key_split_shape(B, S, H, head_dim)) {
         a.o_part = workspace;
@@ -3028,11 +2978,16 @@ extern "C" int gaot_attention_fwd_dropout(const float* q, const float* k, const 
                                           float* lse, float p_drop, const uint64_t* seed, gaot_stream_t stream) {
     GAOT_REQUIRE(q && k && v && o && lse, "attention_fwd_dropout: null pointer");
     GAOT_REQUIRE(B > 0 && S > 0 && H > 0 && Hkv > 0 && H % Hkv == 0, "attention_fwd_dropout: bad sizes B=%d S=%d H=%d Hkv=%d", B, S, H, Hkv);
-    GAOT_REQUIRE(head_dim > 0 && head_dim <= 128, "attention_fwd_dropout: head_dim %d not in 1..128", head_dim);
+    GAOT_REQUIRE(head_dim > 0 && head_dim <= 256, "attention_fwd_dropout: head_dim %d not in 1..256", head_dim);
     AttnArgs a = {};
     fill_common(a, q, k, v, ldq, ldk, ldv, B, S, H, Hkv, head_dim);
     a.o = o; a.ldo = ldo; a.lse = lse;
     if (int rc = fill_dropout(a, p_drop, seed)) return rc;
+    if (head_dim > 128) {
+        attn_wide_fwd_launch(a, true, ST(stream));
+        GAOT_CHECK_LAUNCH("gaot_attention_fwd_dropout");
+        return GAOT_OK;
+    }
     dim3 grid(cdiv(S, 128) * B * H), block(256);
     if (head_dim <= 32)      hipLaunchKernelGGL((attn_fwd_kernel<32, true>), grid, block, 0, ST(stream), a);
     else if (head_dim <= 64) hipLaunchKernelGGL((attn_fwd_kernel<64, true>), grid, block, 0, ST(stream), a);
@@ -3048,7 +3003,7 @@ extern "C" int gaot_attention_bwd_dropout(const float* q, const float* k, const 
                                           gaot_stream_t stream) {
     GAOT_REQUIRE(q && k && v && o && dout && lse && dq && dk && dv && workspace, "attention_bwd_dropout: null pointer");
     GAOT_REQUIRE(B > 0 && S > 0 && H > 0 && Hkv > 0 && H % Hkv == 0, "attention_bwd_dropout: bad sizes");
-    GAOT_REQUIRE(head_dim > 0 && head_dim <= 128, "attention_bwd_dropout: head_dim %d not in 1..128", head_dim);
+    GAOT_REQUIRE(head_dim > 0 && head_dim <= 256, "attention_bwd_dropout: head_dim %d not in 1..256", head_dim);
     AttnArgs a = {};
     fill_common(a, q, k, v, ldq, ldk, ldv, B, S, H, Hkv, head_dim);
     a.vec = a.vec && (ldo % 4 == 0) && aligned16(dout);
@@ -3060,6 +3015,11 @@ extern "C" int gaot_attention_bwd_dropout(const float* q, const float* k, const 
     if (int rc = fill_dropout(a, p_drop, seed)) return rc;
     const int DP = head_dim <= 32 ? 32 : (head_dim <= 64 ? 64 : 128);
     hipLaunchKernelGGL(attn_delta_kernel, dim3(cdiv((long)B * S * H, 256)), dim3(256), 0, ST(stream), a);
+    if (head_dim > 128) {        // two passes (dK / dV, then dQ): no dQ partials, no reduce
+        attn_wide_bwd_launch(a, true, ST(stream));
+        GAOT_CHECK_LAUNCH("gaot_attention_bwd_dropout");
+        return GAOT_OK;
+    }
     dim3 grid(a.n_kblocks * B * H), block(256);
     if (DP == 32) {
         hipLaunchKernelGGL((attn_bwd_kernel<32, true>), grid, block, bwd_lds_bytes<32>(), ST(stream), a);
@@ -3088,6 +3048,7 @@ extern "C" int gaot_attention_bwd_dropout(const float* q, const float* k, const 
 }
 
 extern "C" int64_t gaot_attention_bwd_workspace(int32_t B, int32_t S, int32_t H, int32_t head_dim) {
+    if (head_dim > 128) return (int64_t)B * H * S;      // 128 < head_dim <= 256: delta only (the dQ pass writes dQ itself)
     const int DP = head_dim <= 32 ? 32 : (head_dim <= 64 ? 64 : 128);
     const int64_t nkb = cdiv(S, 128);
     return (int64_t)B * H * S + nkb * B * H * S * DP;   // delta + dQ partials per key block
@@ -3104,7 +3065,7 @@ extern "C" int gaot_attention_bwd(const float* q, const float* k, const float* v
     const int g_attn_pp = ::g_attn_pp >= 0 ? ::g_attn_pp : (pieces == 2 ? 22 : 33);
     const int g_attn_op = ::g_attn_op >= 0 ? ::g_attn_op : (pieces == 2 ? 2 : 3);
     GAOT_REQUIRE(B > 0 && S > 0 && H > 0 && Hkv > 0 && H % Hkv == 0, "attention_bwd: bad sizes");
-    GAOT_REQUIRE(head_dim > 0 && head_dim <= 128, "attention_bwd: head_dim %d not in 1..128", head_dim);
+    GAOT_REQUIRE(head_dim > 0 && head_dim <= 256, "attention_bwd: head_dim %d not in 1..256", head_dim);
     AttnArgs a = {};
     fill_common(a, q, k, v, ldq, ldk, ldv, B, S, H, Hkv, head_dim);
     a.vec = a.vec && (ldo % 4 == 0) && aligned16(dout);
@@ -3115,6 +3076,18 @@ extern "C" int gaot_attention_bwd(const float* q, const float* k, const float* v
     a.n_kblocks = cdiv(S, 128);
     a.qkv_amax = qkv_absmax; a.dout_amax = dout_absmax; a.dqkv_amax = dqkv_absmax;
     bool dkdv_published = false;
+    if (head_dim > 128) {        // 128 < head_dim <= 256 (attention_wide.hip): delta, the dK / dV pass, the dQ pass
+        if (a.vec && aligned16(o)) hipLaunchKernelGGL(attn_delta_vec_kernel, dim3(cdiv((long)B * S * H * 8, 256)), dim3(256), 0, ST(stream), a, 8);
+        else                       hipLaunchKernelGGL(attn_delta_kernel, dim3(cdiv((long)B * S * H, 256)), dim3(256), 0, ST(stream), a);
+        attn_wide_bwd_launch(a, false, ST(stream));
+        GAOT_CHECK_LAUNCH("gaot_attention_bwd");
+        if (dqkv_absmax) {       // these kernels publish nothing: one grouped-absmax launch over dQ, dK and dV
+            gaot_absmax_item it[3] = {{dq, lddq, B * S, H * head_dim, dqkv_absmax}, {dk, lddk, B * S, H * head_dim, dqkv_absmax},
+                                      {dv, lddv, B * S, H * head_dim, dqkv_absmax}};
+            if (int rc = gaot_absmax_grouped(it, 3, stream)) return rc;
+        }
+        return GAOT_OK;
+    }
     const int DP = head_dim <= 32 ? 32 : (head_dim <= 64 ? 64 : 128);
     const bool split_ok = head_dim == 32 && a.vec && g_attn_split && aligned16(dq) && aligned16(dk) && aligned16(dv);
     // 128 .. 255 workgroups of 256 keys: the query tiles of a key block go to two workgroups (attn_bwd_split8_kernel QS = 2)

@@ -100,8 +100,8 @@ class GroupQueryFlashAttention(nn.Module):
             if self.head_dim % 2:
                 raise ValueError("rope needs an even head_dim")
             self.rotary_emb = RotaryEmbedding(dim=self.head_dim)
-        if self.head_dim > 128:
-            raise NotImplementedError("the attention kernels support head_dim <= 128")
+        if self.head_dim > 256:
+            raise NotImplementedError("the attention kernels support head_dim <= 256")
 
     def forward(self, x, condition=None, relative_positions=None, residual=None):
         if self.correction is not None:

@@ -374,7 +374,8 @@ int gaot_act_bwd(const float* g, const float* z, int64_t n, int32_t act, float* 
 /* softmax attention, no mask, scale 1/sqrt(head_dim) (attn.py:98-116, F.scaled_dot_product_attention).
  * q/k/v are strided views: element (b,s,h,d) at ptr[(b*S+s)*ld + h*head_dim + d]; kv head = h / (H/Hkv).
  * o has the same addressing with ldo.  lse[B,H,S] (natural-log-sum-exp of scaled scores) saved for bwd.
- * head_dim <= 128, S arbitrary (head_dim <= 64: split-bf16 kernels where they apply; above: fp32 MFMA).
+ * head_dim <= 256, S arbitrary (head_dim <= 64: split-bf16 kernels where they apply; above: fp32 MFMA; above 128 the head dimension
+ * is split over the four waves of a workgroup, `pieces` is accepted and ignored as for 64 < head_dim <= 128).
  * pieces: precision of the products on the matrix pipe, as gaot_gemm_desc.pieces: 0 / 3 = every fp32 operand (Q, K, V, dO and the
  * probabilities P / dS) as three bf16 pieces, exact to fp32 rounding; 2 = two rounded bf16 pieces each (16 significant bits); 4 = two
  * fp16 pieces of the scaled operand (head_dim 32; elsewhere, and without the words, it means 3): Q / K / V scaled through
@@ -391,12 +392,14 @@ int64_t gaot_attention_fwd_workspace(int32_t B, int32_t S, int32_t H, int32_t he
 int gaot_attention_fwd_ws(const float* q, const float* k, const float* v, int64_t ldq, int64_t ldk, int64_t ldv,
                           int32_t B, int32_t S, int32_t H, int32_t Hkv, int32_t head_dim,
                           float* o, int64_t ldo, float* lse, int32_t pieces, const float* qkv_absmax, float* workspace, gaot_stream_t stream);
-/* workspace floats needed by gaot_attention_bwd */
+/* workspace floats needed by gaot_attention_bwd (gaot_attention_bwd_workspace below): head_dim <= 128: B*H*S (delta) +
+ * cdiv(S, 128) slabs of B*H*S*DP dQ partials, DP = 32 / 64 / 128 the padded head_dim; 128 < head_dim <= 256: B*H*S (delta only:
+ * that backward runs a dK / dV pass and a dQ pass and writes no partials). */
 /* attention dropout (attn.py:110-114: dropout_p of F.scaled_dot_product_attention while training): the softmax output is
  * multiplied by keep(b,h,q,k) / (1 - p) before the product with V.  keep = (splitmix64(seed + ((b*H + h)*S + q)*S + k) >> 32) <
  * (1 - p) * 2^32 with seed read from DEVICE memory, so captured graphs draw a new mask at every replay:
  *   gaot_attention_seed_next : used[0] = mix(state[0], state[1] + 1, salt); state[1] += 1   (state = {seed, counter})
- *   gaot_attention_fwd_dropout / _bwd_dropout : as gaot_attention_fwd / _bwd (fp32-MFMA kernels, head_dim <= 128) with p_drop in (0, 1) and the
+ *   gaot_attention_fwd_dropout / _bwd_dropout : as gaot_attention_fwd / _bwd (fp32-MFMA kernels, head_dim <= 256) with p_drop in (0, 1) and the
  *   device word written by gaot_attention_seed_next; the backward regenerates the forward's mask from the same word. */
 int gaot_attention_seed_next(uint64_t* state, uint64_t salt, uint64_t* used, gaot_stream_t stream);
 int gaot_attention_fwd_dropout(const float* q, const float* k, const float* v, int64_t ldq, int64_t ldk, int64_t ldv,
