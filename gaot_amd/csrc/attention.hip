@@ -2815,6 +2815,22 @@ __global__ void attn_add_cols_kernel(float* a, long lda, const float* a2, float*
     }
 }
 
+// S == 1: one key, so the softmax is 1 and out[b,h,:] = v[b,hk,:] -- a copy, exact by construction (the general kernels reach it only to
+// fp32 rounding: two fp16 pieces carry 22 bits of v, and exp2(fma(s, c, -rn(m c))) is 1 - 2^-24 where rn(m c) rounded up); lse = scale <q, k>.
+// One wave per (b, h); scalar loads and stores: any base, any pitch.
+__global__ __launch_bounds__(64) void attn_fwd_one_key_kernel(const AttnArgs p) {
+    const int bh = blockIdx.x, b = bh / p.H, h = bh % p.H, hk = h / (p.H / p.Hkv);
+    const float* q = p.q + (long)b * p.ldq + (long)h * p.D;
+    const float* k = p.k + (long)b * p.ldk + (long)hk * p.D;
+    const float* v = p.v + (long)b * p.ldv + (long)hk * p.D;
+    float* o = p.o + (long)b * p.ldo + (long)h * p.D;
+    float acc = 0.f;
+    for (int d = threadIdx.x; d < p.D; d += 64) { acc = fmaf(q[d], k[d], acc); o[d] = v[d]; }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (threadIdx.x == 0) p.lse[bh] = acc * p.scale;
+}
+
 static int fill_common(AttnArgs& a, const float* q, const float* k, const float* v, int64_t ldq, int64_t ldk, int64_t ldv,
                        int B, int S, int H, int Hkv, int D) {
     a.q = q; a.k = k; a.v = v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
@@ -2896,6 +2912,11 @@ extern "C" int gaot_attention_fwd_ws(const float* q, const float* k, const float
     AttnArgs a = {};
     fill_common(a, q, k, v, ldq, ldk, ldv, B, S, H, Hkv, head_dim);
     a.o = o; a.ldo = ldo; a.lse = lse; a.qkv_amax = qkv_absmax;
+    if (S == 1) {                // a single key: out = v exactly, every head_dim, every `pieces`
+        hipLaunchKernelGGL(attn_fwd_one_key_kernel, dim3(B * H), dim3(64), 0, ST(stream), a);
+        GAOT_CHECK_LAUNCH("gaot_attention_fwd");
+        return GAOT_OK;
+    }
     if (head_dim > 128) {        // 128 < head_dim <= 256: fp32 MFMA with the head dimension split over the waves (attention_wide.hip)
         attn_wide_fwd_launch(a, false, ST(stream));
         GAOT_CHECK_LAUNCH("gaot_attention_fwd");
@@ -3092,7 +3113,7 @@ extern "C" int gaot_attention_bwd(const float* q, const float* k, const float* v
     const bool split_ok = head_dim == 32 && a.vec && g_attn_split && aligned16(dq) && aligned16(dk) && aligned16(dv);
     // 128 .. 255 workgroups of 256 keys: the query tiles of a key block go to two workgroups (attn_bwd_split8_kernel QS = 2)
     const long wg8 = (long)cdiv(S, 256) * B * H;
-    const bool qsplit = f16 && split_ok && aligned16(o) && g_attn_split == 1 && g_attn_qsplit && wg8 >= 128 && wg8 < 256 && cdiv(S, 32) >= 8 && cdiv(S, 128) - cdiv(S, 256) >= 2;          // (two spare dQ slabs for the second half's dK / dV)
+    const bool qsplit = f16 && split_ok && aligned16(o) && lddk % 4 == 0 && lddv % 4 == 0 && aligned16(a.dq_part) && g_attn_split == 1 && g_attn_qsplit && wg8 >= 128 && wg8 < 256 && cdiv(S, 32) >= 8 && cdiv(S, 128) - cdiv(S, 256) >= 2;          // (two spare dQ slabs for the second half's dK / dV)
     const bool fused_delta = f16 && split_ok && aligned16(o) && g_attn_split != 3 && (g_attn_split == 2 || wg8 >= 256 || qsplit);   // the fp16 8-wave kernel forms delta itself
     if (fused_delta) {
     } else if (a.vec && aligned16(o)) {
@@ -3138,7 +3159,7 @@ extern "C" int gaot_attention_bwd(const float* q, const float* k, const float* v
     } else if (head_dim > 32 && head_dim <= 64 && a.vec && g_attn_split && aligned16(dq) && aligned16(dk) && aligned16(dv)) {
         const long wg8d = (long)cdiv(S, 256) * B * H;
         // [r6] fp16 pieces on eight waves: 256-key blocks when they fill the chip, shared between two workgroups (QS = 2) at 128 .. 255 blocks
-        const bool f16_qs = f16 && g_attn_dh8 && g_attn_split != 3 && wg8d >= 128 && wg8d < 256 && cdiv(S, 32) >= 8 && cdiv(S, 128) - cdiv(S, 256) >= 2;
+        const bool f16_qs = f16 && g_attn_dh8 && g_attn_split != 3 && lddk % 4 == 0 && lddv % 4 == 0 && aligned16(a.dq_part) && wg8d >= 128 && wg8d < 256 && cdiv(S, 32) >= 8 && cdiv(S, 128) - cdiv(S, 256) >= 2;
         if (f16 && g_attn_dh8 && g_attn_split != 3 && wg8d >= 256) {
             a.n_kblocks = cdiv(S, 256);
             hipLaunchKernelGGL((attn_bwd_split8_dh_kernel<true, 1>), dim3(a.n_kblocks * B * H), dim3(512), 0, ST(stream), a);
@@ -3181,7 +3202,7 @@ extern "C" int gaot_attention_bwd(const float* q, const float* k, const float* v
     }
     const long total = (long)B * H * S * DP;
     int nb = cdiv(total, 256); if (nb > 4096) nb = 4096;
-    const bool vec_ok = head_dim % 4 == 0 && aligned16(dq) && lddq % 4 == 0 && total < (1L << 31);
+    const bool vec_ok = head_dim % 4 == 0 && aligned16(dq) && lddq % 4 == 0 && aligned16(a.dq_part) && total < (1L << 31);
     if (vec_ok && DP == 32 && head_dim == 32)
         hipLaunchKernelGGL(attn_dq_reduce_vec_kernel<8>, dim3(cap_blocks(total / 4, 256, 1024)), dim3(256), 0, ST(stream), a);
     else if (vec_ok && DP == 64)

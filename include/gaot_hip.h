@@ -380,7 +380,13 @@ int gaot_act_bwd(const float* g, const float* z, int64_t n, int32_t act, float* 
  * probabilities P / dS) as three bf16 pieces, exact to fp32 rounding; 2 = two rounded bf16 pieces each (16 significant bits); 4 = two
  * fp16 pieces of the scaled operand (head_dim 32; elsewhere, and without the words, it means 3): Q / K / V scaled through
  * qkv_absmax -- ONE magnitude word for the three of them (they are column blocks of one projection output; any bound works) --
- * dO through dout_absmax, P by 2^13, dS per 32 x 32 tile by the tile's own maximum. */
+ * dO through dout_absmax, P by 2^13, dS per 32 x 32 tile by the tile's own maximum.
+ * S = 1 (one key, softmax = 1): o is v of the kv head bit for bit, lse = scale <q, k> (a copy kernel; dropout excepted).
+ * Backward with Hkv < H: dk and dv receive one block per QUERY head -- B*S rows of H * head_dim columns each (element (b,s,h,d) at
+ * ptr[(b*S+s)*ld + h*head_dim + d], as dq) -- and the caller sums the H / Hkv blocks of a kv head; a buffer sized for Hkv * head_dim
+ * columns is too small.
+ * Alignment: any base pointer and any pitch >= the used columns are accepted for q, k, v, o, dout, dq, dk and dv; the 16-byte kernels
+ * run where head_dim, the pitches and the base addresses they touch are multiples of 4 floats / 16 bytes, the scalar ones elsewhere. */
 int gaot_attention_fwd(const float* q, const float* k, const float* v, int64_t ldq, int64_t ldk, int64_t ldv,
                        int32_t B, int32_t S, int32_t H, int32_t Hkv, int32_t head_dim,
                        float* o, int64_t ldo, float* lse, int32_t pieces, const float* qkv_absmax, gaot_stream_t stream);
@@ -405,6 +411,7 @@ int gaot_attention_seed_next(uint64_t* state, uint64_t salt, uint64_t* used, gao
 int gaot_attention_fwd_dropout(const float* q, const float* k, const float* v, int64_t ldq, int64_t ldk, int64_t ldv,
                                int32_t B, int32_t S, int32_t H, int32_t Hkv, int32_t head_dim, float* o, int64_t ldo,
                                float* lse, float p_drop, const uint64_t* seed, gaot_stream_t stream);
+/* (Hkv < H: dk and dv receive one block per QUERY head, H * head_dim columns, and the caller sums over the group -- as gaot_attention_bwd) */
 int gaot_attention_bwd_dropout(const float* q, const float* k, const float* v, int64_t ldq, int64_t ldk, int64_t ldv,
                                const float* o, const float* dout, int64_t ldo, const float* lse, int32_t B, int32_t S,
                                int32_t H, int32_t Hkv, int32_t head_dim, float* dq, float* dk, float* dv, int64_t lddq,
