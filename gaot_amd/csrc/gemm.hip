@@ -214,7 +214,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_kernel(const GemmArgs p) {
     }
     if (p.vec_epi) {
         __syncthreads();                                   // all waves are done with As / Bs
-        epilogue_vec<TM, TN, WM, WN>(p, smem, acc, m0, n0, wm, wn, wave, lane);
+        epilogue_vec<TM, TN, WM, WN, 2>(p, smem, acc, m0, n0, wm, wn, wave, lane);
         return;
     }
     // scalar fallback epilogue (odd N / unaligned operands): C-layout rows crow(r, lh), column li
@@ -376,6 +376,8 @@ extern "C" unsigned gaot_debug_split_redo_count(int reset) { return gaot::split_
 extern "C" int gaot_debug_set_gemm_planes(int on) { const int old = g_use_planes; g_use_planes = on; return old; }
 static int g_ablate = 0;
 extern "C" int gaot_debug_set_gemm_ablate(int bits) { const int old = g_ablate; g_ablate = bits; return old; }
+static int g_aux_prefetch = 1;   // vector epilogues of the acts that read aux_in: 1 = a band's aux vectors issued together ahead of its LDS transpose, 0 = pass by pass (A/B switch; bit-identical)
+extern "C" int gaot_debug_set_gemm_aux_prefetch(int on) { const int old = g_aux_prefetch; g_aux_prefetch = on ? 1 : 0; return old; }
 static int g_tile_override = 0;   // tuning hook: 0 = heuristic, 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 128x32
 extern "C" int gaot_debug_set_gemm_tile(int cfg) { const int old = g_tile_override; g_tile_override = cfg; return old; }
 
@@ -427,6 +429,7 @@ static int gemm_run(const gaot_gemm_desc* d, gaot_stream_t stream, const bool dr
     a.split_k = split; a.ktiles_per_split = cdiv(nkt, split); a.ws = d->workspace;
     a.colsum = d->colsum;
     a.ablate = g_ablate;
+    a.aux_pf = g_aux_prefetch;
     a.a_amax = pieces >= 4 ? d->a_absmax : nullptr; a.b_amax = pieces >= 4 ? d->b_absmax : nullptr; a.c_amax = d->c_absmax;
     a.a2_amax = pieces >= 4 ? d->a2_absmax : nullptr;
     // B pre-split into fp16 planes (weights, once per pass): only the split tiles with fp16 pieces read them
@@ -538,6 +541,8 @@ static int gemm_run(const gaot_gemm_desc* d, gaot_stream_t stream, const bool dr
         // rounds (8192 x 2048 x 256: 49 -> 51-54 us; x 768: 23.2 -> 26.8 on 64-row tiles) and the K-slab products (8192 x 256 x 2048 in
         // two slabs: 42.9 -> 42.6) stay on the staged kernel -- there the output stores / the slab count decide.  Step level
         // (tools/step_ab.py, same box): C2 2.3225 -> 2.2666 ms, C4-shaped 1.8169 -> 1.7888
+        // Re-checked with the epilogue's aux prefetch in (tools/bin/ad_bench swiglu, u from HBM): the SwiGLU-gradient product 8192 x 1024 x 256
+        // 39.8-43.0 us on the 128-row tiles (one round) against 42.3-42.6 on the 64-row ones (two rounds): the rule stays
         const bool ad_ok = g_use_ad && pieces == 4 && a.Bpl != nullptr && ak && a.K % 32 == 0 && a.vec_epi && (a.A2 == nullptr || a.k_split % 32 == 0);
         const bool ad64 = ad_ok && (g_use_ad == 2 || (a.split_k <= 1 && (cdiv(a.N, 128) <= 2 || blocks(64, 128) <= 512) && blocks(64, 128) >= 128));
         const bool ad128 = ad_ok && !ad64 && !big && (g_use_ad == 3 || (a.split_k <= 1 && split128 && blocks(128, 128) <= 512));

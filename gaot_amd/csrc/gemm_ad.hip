@@ -359,7 +359,7 @@ __global__ __launch_bounds__(256, 2) void gemm_ad_kernel(const GemmArgs p) {
 
     if (ABL & 4) { if (acc[0][0][0] + acc[TM - 1][TN - 1][3] == 123.456f) p.C[tid] = 1.f; return; }
     if (p.act == GAOT_ACT_SWIGLU) epilogue_swiglu<TM, TN, WM, WN>(p, reinterpret_cast<float*>(smem_raw), acc, m0, n0, wm, wn, wave, lane, so_a, so_b);
-    else epilogue_vec<TM, TN, WM, WN>(p, reinterpret_cast<float*>(smem_raw), acc, m0, n0, wm, wn, wave, lane, zs, so_a, so_b);
+    else epilogue_vec<TM, TN, WM, WN, 4>(p, reinterpret_cast<float*>(smem_raw), acc, m0, n0, wm, wn, wave, lane, zs, so_a, so_b);          // (aux vectors of 2 x 4 passes in flight: 16 KB per wave on the 128 x 128 tiles, several times what the memory latency asks of a CU's eight waves; 8 passes a batch spill there)
 }
 
 unsigned ad_redo_count(bool reset) {

@@ -22,6 +22,8 @@ struct GemmArgs {
     int bpl_flag;           // with Bpl: which float of b_amax's first line holds the planes' range verdict (1: along rows, 2: along columns of W as stored)
     float* c_amax;          // optional: max |C| as stored, accumulated by atomic max on the float's bit pattern (zero before the launch)
     int ablate;             // tuning only (gaot_debug_set_gemm_ablate): 1 = no in-loop global loads, 2 = no LDS staging/barriers, 4 = no stores
+    int aux_pf;             // vector epilogue, acts that read aux_in: 1 = a band's aux vectors are issued together ahead of its LDS transpose (default,
+                            // gaot_debug_set_gemm_aux_prefetch), 0 = loaded pass by pass; same values either way
 };
 
 // SwiGLU gate and its gradient (attn.py:151): g = silu(u1) * u3
@@ -29,6 +31,14 @@ __device__ __forceinline__ float swiglu_f(float u1, float u3) { return (u1 / (1.
 __device__ __forceinline__ void swiglu_grad_f(float dg, float u1, float u3, float& d1, float& d3) {
     const float sg = 1.0f / (1.0f + expf(-u1));
     d1 = dg * u3 * sg * (1.0f + u1 * (1.0f - sg));
+    d3 = dg * u1 * sg;
+}
+// the same for the vector epilogue, with the one contraction the expression offers written out: whether `1 + u1 (1 - sg)` becomes an fma is
+// otherwise decided per element by how the compiler packs the surrounding code into two-wide instructions, and the epilogue's two
+// forms (aux vectors pass by pass / issued ahead) must round alike to the last bit
+__device__ __forceinline__ void swiglu_grad_vec_f(float dg, float u1, float u3, float& d1, float& d3) {
+    const float sg = 1.0f / (1.0f + expf(-u1));
+    d1 = dg * u3 * sg * __builtin_fmaf(u1, 1.0f - sg, 1.0f);
     d3 = dg * u1 * sg;
 }
 
@@ -98,7 +108,19 @@ __device__ __forceinline__ void epilogue_store_row(const GemmArgs& p, const RowC
 // slab (the MFMA C-layout puts a COLUMN in a lane; stores want 4 consecutive columns per lane) and then does bias / row
 // bias / row scale / activation / residual / store on 16-byte vectors: 4x fewer store instructions, 128-256 B per row.
 // The caller must have synchronised the workgroup (smem is reused) and smem must hold NW * 32 * (WN + 4) floats.
-template <int TM, int TN, int WM, int WN>
+//
+// PF > 0 (and p.aux_pf at run time): the acts that read aux_in (GELU_BWD / RELU_BWD: one vector per pass, SWIGLU_BWD: two) issue the aux
+// vectors of a band in batches of PF passes, two batches in flight -- the first ahead of the band's LDS transpose, the next one in front
+// of the arithmetic of the batch in hand -- instead of one pass's worth in front of every pass's arithmetic.  aux_in is a saved activation
+// written a whole forward pass earlier: every load goes to HBM, and pass by pass a wave sits through a band's 8-16 rounds of that latency
+// one after the other with one or two loads in flight (and, the memory counter being one in-order counter, through the previous pass's
+// stores as well).  The batched form runs as straight-line code -- the compiler then counts its waits instead of draining the counter at
+// every join of a per-pass branch -- so it serves the bands that lie wholly inside M (wave-uniform; all but the last tile row's) of
+// products without row bias / row scale / aux_out / residual; every other band takes the pass-by-pass loop below.  Same addresses, same
+// arithmetic in the same order: bit-identical results; a lane outside N loads nothing, and no row outside M is addressed.  Registers:
+// 4 (SwiGLU: 8) per pass in flight, of which only the first batch overlaps the band's live accumulators.
+template <bool B> struct EpiTag { static constexpr bool value = B; };
+template <int TM, int TN, int WM, int WN, int PF = 0>
 __device__ __forceinline__ void epilogue_vec(const GemmArgs& p, float* smem, const f32x16 (&acc)[TM][TN], int m0, int n0,
                                          int wm, int wn, int wave, int lane, int zs = -1, float so1 = 1.f, float so2 = 1.f) {
     float amax = 0.f;
@@ -117,8 +139,76 @@ __device__ __forceinline__ void epilogue_vec(const GemmArgs& p, float* smem, con
     f32x4 bv = {0.f, 0.f, 0.f, 0.f};
     if (p.bias && nok && p.split_k <= 1) bv = *reinterpret_cast<const f32x4*>(p.bias + n);
     const bool has_auxin = (p.act == GAOT_ACT_GELU_BWD || p.act == GAOT_ACT_RELU_BWD);
+    constexpr int NPS = 32 / RPP;                      // passes per band
+    constexpr int NB = PF <= 0 ? 0 : (PF < NPS ? PF : NPS);          // passes per batch of aux vectors
+    const bool aux_pf = NB > 0 && p.aux_pf != 0 && p.split_k <= 1 && (has_auxin || p.act == GAOT_ACT_SWIGLU_BWD) &&
+                        !p.rowbias && !p.rowscale && !p.aux_out && !p.residual;
+    // one band, wholly inside M, with its aux vectors issued ahead (SW: SwiGLU gradient, two vectors per pass; else GELU / ReLU gradient, one)
+    auto band_pf = [&](auto sw_tag, int i) __attribute__((always_inline)) {
+        constexpr bool SW = decltype(sw_tag)::value;
+        constexpr int NBB = NB > 0 ? NB : 1;
+        constexpr int NBAT = NPS / NBB;
+        static_assert(NPS % NBB == 0, "the batches tile the band");
+        f32x4 a1[2][NBB], a3[2][SW ? NBB : 1];
+        const int mb = m0 + wm * WM + i * 32 + lr;          // this lane's row in pass 0
+        const float* ax0 = p.aux_in + (long)mb * p.ld_aux + n;
+        auto issue = [&](int bt) __attribute__((always_inline)) {
+#pragma unroll
+            for (int q = 0; q < NBB; ++q) {
+                const float* ax = ax0 + (long)((bt * NBB + q) * RPP) * p.ld_aux;
+                a1[bt & 1][q] = *reinterpret_cast<const f32x4*>(ax);
+                if (SW) a3[bt & 1][q] = *reinterpret_cast<const f32x4*>(ax + p.N);
+            }
+        };
+        if (nok) issue(0);
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) Cw[crow(r, lh) * LDC_S + j * 32 + li] = acc[i][j][r];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (nok) {
+#pragma unroll
+            for (int bt = 0; bt < NBAT; ++bt) {
+                if (bt + 1 < NBAT) issue(bt + 1);
+#pragma unroll
+                for (int q = 0; q < NBB; ++q) {
+                    const int row = (bt * NBB + q) * RPP + lr;
+                    const int m = mb + (bt * NBB + q) * RPP;
+                    f32x4 v = *reinterpret_cast<const f32x4*>(Cw + row * LDC_S + lc) * so1 * so2;
+                    v += bv;
+                    if (!SW) {
+                        const f32x4 ax = a1[bt & 1][q];
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            v[e] = (p.act == GAOT_ACT_GELU_BWD) ? v[e] * gelu_grad_f(ax[e]) : (ax[e] > 0.f ? v[e] : 0.f);
+                    } else {
+                        const f32x4 u1 = a1[bt & 1][q], u3 = a3[bt & 1][SW ? q : 0];
+                        f32x4 d3;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) { float d1, d3e; swiglu_grad_vec_f(v[e], u1[e], u3[e], d1, d3e); v[e] = d1; d3[e] = d3e; }
+                        *reinterpret_cast<f32x4*>(p.C + (long)m * p.ldc + p.N + n) = d3;
+                        amax = fmaxf(amax, fmaxf(fmaxf(fabsf(d3[0]), fabsf(d3[1])), fmaxf(fabsf(d3[2]), fabsf(d3[3]))));
+                    }
+                    *reinterpret_cast<f32x4*>(p.C + (long)m * p.ldc + n) = v;
+                    amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
+        if constexpr (NB > 0) {
+            if (aux_pf && m0 + wm * WM + i * 32 + 32 <= p.M) {
+                if (p.act == GAOT_ACT_SWIGLU_BWD) band_pf(EpiTag<true>{}, i);
+                else band_pf(EpiTag<false>{}, i);
+                continue;
+            }
+        }
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
@@ -155,7 +245,7 @@ __device__ __forceinline__ void epilogue_vec(const GemmArgs& p, float* smem, con
                         const f32x4 u3 = *reinterpret_cast<const f32x4*>(p.aux_in + (long)m * p.ld_aux + p.N + n);
                         f32x4 d3;
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) { float d1, d3q; swiglu_grad_f(v[q], u1[q], u3[q], d1, d3q); v[q] = d1; d3[q] = d3q; }
+                        for (int q = 0; q < 4; ++q) { float d1, d3q; swiglu_grad_vec_f(v[q], u1[q], u3[q], d1, d3q); v[q] = d1; d3[q] = d3q; }
                         *reinterpret_cast<f32x4*>(p.C + (long)m * p.ldc + p.N + n) = d3;
                         amax = fmaxf(amax, fmaxf(fmaxf(fabsf(d3[0]), fabsf(d3[1])), fmaxf(fabsf(d3[2]), fabsf(d3[3]))));
                     }

@@ -179,7 +179,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_glds_kernel(const GemmArgs p) {
     }
     __syncthreads();
     if (BKM && p.act == GAOT_ACT_SWIGLU) epilogue_swiglu<TM, TN, WM, WN>(p, smem, acc, m0, n0, wm, wn, wave, lane);
-    else                                 epilogue_vec<TM, TN, WM, WN>(p, smem, acc, m0, n0, wm, wn, wave, lane);
+    else                                 epilogue_vec<TM, TN, WM, WN, 2>(p, smem, acc, m0, n0, wm, wn, wave, lane);
 }
 
 static int g_glds_stages = 2;     // 2-stage ring: half the LDS -> twice the resident workgroups; measured ahead of 3 stages

@@ -619,8 +619,12 @@ __device__ __forceinline__ void split_tile(const GemmArgs& p, unsigned char* sme
         __syncthreads();
     }
     if (ABL & 4) { if (acc[0][0][0] + acc[1][1][3] + acc[0][1][5] + acc[1][0][7] == 123.456f) p.C[tid] = 1.f; __syncthreads(); return; }
+    // aux vectors of the *_BWD acts ahead of the band's transpose (gemm_common.h), two passes a batch: compiled out where it would cost what the
+    // kernel has not got -- the grouped weight-gradient launch (FLUSH != 0: no act, 168 registers with spills), the 256-row tiles (a wave
+    // of occupancy) and the 128-row fp16-piece tiles that stage an unsplit m-major B (at the 168-register ceiling: two to three more spills)
+    constexpr int AUX_PF = (FLUSH != 0 || BM == 256 || (NP == 4 && BM == 128 && !BKM)) ? 0 : 2;
     if (BKM && p.act == GAOT_ACT_SWIGLU) epilogue_swiglu<TM, TN, WM, WN>(p, reinterpret_cast<float*>(smem_raw), acc, m0, n0, wm, wn, wave, lane, so_a, so_b);
-    else epilogue_vec<TM, TN, WM, WN>(p, reinterpret_cast<float*>(smem_raw), acc, m0, n0, wm, wn, wave, lane, zs, so_a, so_b);
+    else epilogue_vec<TM, TN, WM, WN, AUX_PF>(p, reinterpret_cast<float*>(smem_raw), acc, m0, n0, wm, wn, wave, lane, zs, so_a, so_b);          // (AUX_PF: above)
     __syncthreads();          // the epilogue's LDS slabs alias the stages the next tile is about to fill
 }
 
@@ -692,7 +696,7 @@ __global__ __launch_bounds__(BM == 256 ? 512 : 256, BM == 256 ? 1 : 2) void gemm
     a.bias = nullptr; a.rowbias = nullptr; a.rb_period = 0; a.ld_rb = 0; a.rowscale = nullptr; a.act = GAOT_ACT_NONE;
     a.aux_in = nullptr; a.aux_out = nullptr; a.ld_aux = 0; a.residual = nullptr; a.ldr = 0;
     a.split_k = split; a.ktiles_per_split = g.p[i].kt_per_split; a.ws = g.ws + g.p[i].ws_off;
-    a.colsum = g.p[i].colsum; a.tiles_m = g.p[i].tiles_m; a.tiles_n = g.p[i].tiles_n; a.vec_epi = 1; a.ablate = 0;
+    a.colsum = g.p[i].colsum; a.tiles_m = g.p[i].tiles_m; a.tiles_n = g.p[i].tiles_n; a.vec_epi = 1; a.ablate = 0; a.aux_pf = 0;
     a.a_amax = g.p[i].a_amax; a.b_amax = g.p[i].b_amax; a.c_amax = nullptr; a.a2_amax = nullptr;
     a.Bpl = nullptr; a.ld_bpl = 0; a.bpl_stride = 0;
     a.bpl_flag = 0;

@@ -31,6 +31,10 @@ int gaot_debug_set_gemm_pieces(int pieces);
 int gaot_debug_set_gemm_planes(int on);
 /* all-DMA fp16-piece tiles (gemm_ad.hip): 0 off, 1 per the heuristic (default), 2 / 3: 64- / 128-row tiles wherever eligible; returns the old value */
 int gaot_debug_set_gemm_ad(int on);
+/* GEMM vector epilogues of the acts that read aux_in (GELU_BWD / RELU_BWD / SWIGLU_BWD): 1 (default) = the aux vectors of a wave's whole
+ * 32-row band are issued together, ahead of the band's LDS transpose; 0 = one pass's worth in front of every pass's arithmetic (same-box
+ * A/B; bit-identical results); returns the old value */
+int gaot_debug_set_gemm_aux_prefetch(int on);
 /* 64 x 64 all-DMA tiles for narrow outputs (N <= 256), bits: 1 (default) launches that 64 x 128 tiles leave half filled (4 096-token
  * batches), 2 also K <= 256 at full launches (off: slower at step level); 0 none (same-box A/B; see the dispatcher in gemm.hip);
  * returns the old value */

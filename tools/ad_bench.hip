@@ -1,6 +1,7 @@
 // Stand-alone bench + check of the A-direct fp16-piece tiles (gemm_ad.hip) against the LDS-staged ones (gemm_split.hip): same planes,
 // same words; the two must agree BIT FOR BIT (same piece products in the same order), and both are compared with a float64 product.
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Igaot_amd/csrc tools/ad_bench.hip -o tools/bin/ad_bench
+// `ad_bench swiglu [iters]`: the SwiGLU-gradient product alone -- full / without epilogue / without loop traffic, aux prefetch off and on
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -52,7 +53,7 @@ static void run_case(const Case& c, int iters) {
     hipMemcpy(wa, wordA.data(), 4096, hipMemcpyHostToDevice); hipMemcpy(ww, wordW.data(), 4096, hipMemcpyHostToDevice);
     hipMemset(C0, 0, (size_t)M * N * 4); hipMemset(C1, 0xff, (size_t)M * N * 4);
     GemmArgs a{}; a.M = M; a.N = N; a.K = K; a.A = A; a.lda = K; a.B = W; a.ldb = K; a.ldc = NO;
-    a.split_k = c.sk; a.ktiles_per_split = cdiv(K / 32, c.sk); a.vec_epi = 1; a.rb_period = 1; a.act = c.act;
+    a.split_k = c.sk; a.ktiles_per_split = cdiv(K / 32, c.sk); a.vec_epi = 1; a.rb_period = 1; a.act = c.act; a.aux_pf = 1;
     float* ws = nullptr; if (c.sk > 1) { hipMalloc(&ws, (size_t)c.sk * ((size_t)M * N + M) * 4); a.ws = ws; }
     a.a_amax = wa; a.b_amax = ww; a.Bpl = P; a.ld_bpl = 2 * K; a.bpl_stride = 16;
     if (c.act == GAOT_ACT_SWIGLU) { a.aux_out = aux; a.ld_aux = N; }
@@ -137,7 +138,72 @@ static void ablate(int M, int N, int K, int bm, int iters) {
     hipFree(A); hipFree(W); hipFree(P); hipFree(C); hipFree(wa); hipFree(ww);
 }
 
+// The SwiGLU-gradient product of the FFN backward (du = swiglu'(dY w2; u), act = SWIGLU_BWD): how its time splits between the k-loop and
+// the epilogue, and the epilogue's aux prefetch on / off.  u and du rotate through NBUF buffers (NBUF x 128 MB, more than the 256 MB of
+// last-level cache) so that every launch reads u from HBM, as in the step, where u was written a forward pass earlier.
+template <int ABL>
+static float run_swb(GemmArgs a, int bm, int iters, float* const* aux, float* const* out, int nbuf) {
+    a.tiles_m = cdiv(a.M, bm); a.tiles_n = cdiv(a.N, 128); a.bpl_flag = 1;
+    dim3 grid(a.tiles_m * a.tiles_n), block(256);
+    hipEvent_t s, e; hipEventCreate(&s); hipEventCreate(&e);
+    int it = 0;
+    auto go = [&]() {
+        a.aux_in = aux[it % nbuf]; a.C = out[it % nbuf]; ++it;
+        if (bm == 64) hipLaunchKernelGGL((gemm_ad_kernel<64, 2, 3, false, ABL>), grid, block, 0, 0, a);
+        else hipLaunchKernelGGL((gemm_ad_kernel<128, 4, 2, false, ABL>), grid, block, 0, 0, a);
+    };
+    for (int i = 0; i < nbuf; ++i) go();
+    hipEventRecord(s, 0);
+    for (int i = 0; i < iters; ++i) go();
+    hipEventRecord(e, 0); hipEventSynchronize(e);
+    float ms; hipEventElapsedTime(&ms, s, e);
+    hipEventDestroy(s); hipEventDestroy(e);
+    return ms * 1e3f / iters;
+}
+static void swiglu_bwd_split(int M, int N, int K, int iters) {
+    constexpr int NBUF = 6;
+    float *A, *W, *wa, *ww, *aux[NBUF], *out[NBUF]; unsigned short* P;
+    hipMalloc(&A, (size_t)M * K * 4); hipMalloc(&W, (size_t)N * K * 4); hipMalloc(&P, (size_t)N * K * 4);
+    hipMalloc(&wa, 4096); hipMalloc(&ww, 4096);
+    std::vector<float> h((size_t)M * K); for (auto& v : h) v = (float)rand() / RAND_MAX - 0.5f;
+    hipMemcpy(A, h.data(), h.size() * 4, hipMemcpyHostToDevice);
+    std::vector<unsigned short> hp((size_t)N * K * 2); for (auto& v : hp) v = 0x3800 + (rand() & 0x3ff);
+    hipMemcpy(P, hp.data(), hp.size() * 2, hipMemcpyHostToDevice);
+    std::vector<float> word(1024, 0.f); word[0] = 0.5f;
+    hipMemcpy(wa, word.data(), 4096, hipMemcpyHostToDevice); hipMemcpy(ww, word.data(), 4096, hipMemcpyHostToDevice);
+    std::vector<float> hu((size_t)M * 2 * N); for (auto& v : hu) v = ((float)rand() / RAND_MAX - 0.5f) * 4.f;
+    for (int b = 0; b < NBUF; ++b) {
+        hipMalloc(&aux[b], hu.size() * 4); hipMalloc(&out[b], hu.size() * 4);
+        hipMemcpy(aux[b], hu.data(), hu.size() * 4, hipMemcpyHostToDevice);
+    }
+    GemmArgs a{}; a.M = M; a.N = N; a.K = K; a.A = A; a.lda = K; a.B = W; a.ldb = N; a.ldc = 2 * N;
+    a.split_k = 1; a.ktiles_per_split = K / 32; a.vec_epi = 1; a.rb_period = 1; a.act = GAOT_ACT_SWIGLU_BWD; a.ld_aux = 2 * N;
+    a.a_amax = wa; a.b_amax = ww; a.Bpl = P; a.ld_bpl = 2 * K; a.bpl_stride = 16;
+    for (int bm : {128, 64}) {
+        GemmArgs p0 = a, p1 = a; p0.aux_pf = 0; p1.aux_pf = 1;
+        // two rounds, alternating, so that a drift of the clocks shows
+        for (int rnd = 0; rnd < 2; ++rnd)
+            printf("swiglu-bwd M=%d N=%d K=%d bm=%3d | full, aux pass by pass %.1f us | full, aux prefetched %.1f us | without the range watch: %.1f, %.1f | no epilogue %.1f | no loop traffic: pass by pass %.1f, prefetched %.1f | neither %.1f\n",
+                   M, N, K, bm, run_swb<0>(p0, bm, iters, aux, out, NBUF), run_swb<0>(p1, bm, iters, aux, out, NBUF), run_swb<32>(p0, bm, iters, aux, out, NBUF),
+                   run_swb<32>(p1, bm, iters, aux, out, NBUF), run_swb<36>(p1, bm, iters, aux, out, NBUF), run_swb<40>(p0, bm, iters, aux, out, NBUF),
+                   run_swb<40>(p1, bm, iters, aux, out, NBUF), run_swb<44>(p1, bm, iters, aux, out, NBUF));
+    }
+    // the two forms must agree bit for bit (same buffers, one launch each)
+    {
+        GemmArgs p0 = a, p1 = a; p0.aux_pf = 0; p1.aux_pf = 1;
+        hipMemset(out[0], 0, hu.size() * 4); hipMemset(out[1], 0xff, hu.size() * 4);
+        float* one_aux[1] = {aux[0]}; float* o0[1] = {out[0]}; float* o1[1] = {out[1]};
+        run_swb<0>(p0, 128, 1, one_aux, o0, 1); run_swb<0>(p1, 128, 1, one_aux, o1, 1);
+        std::vector<float> h0(hu.size()), h1(hu.size());
+        hipMemcpy(h0.data(), out[0], h0.size() * 4, hipMemcpyDeviceToHost); hipMemcpy(h1.data(), out[1], h1.size() * 4, hipMemcpyDeviceToHost);
+        printf("swiglu-bwd prefetched vs pass by pass: %s | %s\n", memcmp(h0.data(), h1.data(), h0.size() * 4) == 0 ? "bit-identical" : "DIFFERENT", hipGetErrorString(hipDeviceSynchronize()));
+    }
+    hipFree(A); hipFree(W); hipFree(P); hipFree(wa); hipFree(ww);
+    for (int b = 0; b < NBUF; ++b) { hipFree(aux[b]); hipFree(out[b]); }
+}
+
 int main(int argc, char** argv) {
+    if (argc > 1 && strcmp(argv[1], "swiglu") == 0) { swiglu_bwd_split(8192, 1024, 256, argc > 2 ? atoi(argv[2]) : 60); return 0; }
     if (argc > 2) {
         ablate(8192, 2048, 256, 128, 30);
         ablate(8192, 768, 256, 64, 30);
