@@ -188,6 +188,8 @@ PROTOTYPES = {
     "gaot_adamw_step": (C.c_int, [_f, _f, _f, _f, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _f, _s]),
     "gaot_adamw_step_dev": (C.c_int, [_f, _f, _f, _f, C.c_int64, _f, _f, _s]),
     "gaot_adamw_apply_dev": (C.c_int, [_f, _f, _f, _f, C.c_int64, _f, _f, _s]),
+    "gaot_grad_norm_dev": (C.c_int, [_f, C.c_int64, _f, C.c_void_p, _f, _f, C.c_int32, _f, _s]),
+    "gaot_adamw_apply_clipped_dev": (C.c_int, [_f, _f, _f, _f, C.c_int64, _f, _f, _f, _f, _s]),
     "gaot_debug_set_ep_chunk": (C.c_int, [C.c_int]),
     "gaot_gno_ep_workspace": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "gaot_gno_lift_gather_reduce_ep": (C.c_int, [_f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i, _i, _i, C.c_int32, C.c_int32, _f, _f, _f, _i, _s]),

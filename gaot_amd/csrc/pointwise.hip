@@ -417,6 +417,117 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     }
 }
 
+// ---------------------------------------------------------------- global gradient norm + the clip / skip decision, on the device
+// (torch.nn.utils.clip_grad_norm_ and a non-finite guard, folded into the flat update: no host read, hipGraph-replayable).
+// Every workgroup adds its grid-strided slice of sum g^2 (16-byte loads, four in flight, added in index order: one accumulator per
+// thread, so the order -- and the bits -- depend on n alone); the LAST one to take a ticket adds the partials in a fixed order in
+// double and writes gstat[4] = {norm, coef, ok, skipped_total}.  clip[2] = {max_norm, skip_nonfinite} is read at run time.
+// The step counter: with `ticked` the loss launch has already advanced it, so a skipped update takes that tick back; without, this
+// launch advances it unless the update is skipped.  Either way gaot_adamw_apply_clipped_dev finds it final.  The ticket returns to zero.
+__device__ __forceinline__ float sumsq4(const f32x4 a) { return (a[0] * a[0] + a[1] * a[1]) + (a[2] * a[2] + a[3] * a[3]); }
+__global__ __launch_bounds__(256) void grad_norm_kernel(const float* __restrict__ g, long n, float* __restrict__ part, int* __restrict__ ticket,
+                                                        const float* __restrict__ clip, float* __restrict__ step, int ticked,
+                                                        float* __restrict__ gstat) {
+    __shared__ float red[4];
+    __shared__ int last_s;
+    float s = 0.f;
+    const long n4 = n / 4;
+    const long stride = (long)gridDim.x * 256;
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
+    long i = (long)blockIdx.x * 256 + threadIdx.x;
+    for (; i + 3 * stride < n4; i += 4 * stride) {
+        const f32x4 a = g4[i], b = g4[i + stride], c = g4[i + 2 * stride], d = g4[i + 3 * stride];
+        s += sumsq4(a); s += sumsq4(b); s += sumsq4(c); s += sumsq4(d);
+    }
+    for (; i < n4; i += stride) s += sumsq4(g4[i]);
+    if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4 * 4)) {      // scalar tail
+        const float t = g[n4 * 4 + threadIdx.x];
+        s += t * t;
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const int t = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = t == (int)gridDim.x - 1;
+        if (last) {
+            __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        }
+        last_s = last;
+    }
+    __syncthreads();
+    if (!last_s || threadIdx.x >= 64) return;
+    double tot = 0.0;
+    for (int k = threadIdx.x; k < (int)gridDim.x; k += 64) tot += (double)__builtin_nontemporal_load(part + k);
+    tot = wave_sum_d(tot);
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt(tot);
+        const float max_norm = clip[0];
+        const bool skipping = clip[1] != 0.f;
+        const bool ok = isfinite(norm);
+        float coef = 1.0f;
+        if (max_norm > 0.f && !isinf(max_norm)) {          // torch: clamp(max_norm / (norm + 1e-6), max = 1); a NaN norm stays a NaN
+            coef = max_norm / (norm + 1e-6f);
+            coef = coef > 1.0f ? 1.0f : coef;
+        }
+        const bool skip = skipping && !ok;
+        gstat[0] = norm;
+        gstat[1] = coef;
+        gstat[2] = ok ? 1.0f : 0.0f;
+        if (skip) gstat[3] += 1.0f;
+        if (ticked) { if (skip) step[0] -= 1.0f; }
+        else if (!skip) step[0] += 1.0f;
+    }
+}
+static int grad_norm_blocks(int64_t n) { long b = (n / 4 + 1023) / 1024; return (int)(b < 1 ? 1 : (b > 256 ? 256 : b)); }
+
+// adamw_kernel with the gradient multiplied by gstat[1] in registers (the gradient buffer is NOT rewritten); a non-finite norm
+// (gstat[2] == 0) with clip[1] set returns before the first store: p, m, v untouched.
+__global__ __launch_bounds__(256) void adamw_clipped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                            float* __restrict__ v, long n, const float* __restrict__ step,
+                                                            const float* __restrict__ hyper, const float* __restrict__ gstat,
+                                                            const float* __restrict__ clip) {
+    if (gstat[2] == 0.f && clip[1] != 0.f) return;
+    const float coef = gstat[1];
+    const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
+    const float t = step[0];
+    const float bc1 = 1.0f - powf(b1, t);
+    const float bc2 = 1.0f - powf(b2, t);
+    const float step_size = lr / bc1;
+    const float inv_bc2_sqrt = 1.0f / sqrtf(bc2);
+    const long n4 = n / 4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+        f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+        f32x4 mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            gv[q] *= coef;          // coef == 1 is exact: the update below then has adamw_kernel's bits
+            pv[q] *= 1.0f - lr * wd;
+            mv[q] = mv[q] + (gv[q] - mv[q]) * (1.0f - b1);
+            vv[q] = b2 * vv[q] + (1.0f - b2) * gv[q] * gv[q];
+            const float denom = sqrtf(vv[q]) * inv_bc2_sqrt + eps;
+            pv[q] -= step_size * (mv[q] / denom);
+        }
+        reinterpret_cast<f32x4*>(p)[i] = pv;
+        reinterpret_cast<f32x4*>(m)[i] = mv;
+        reinterpret_cast<f32x4*>(v)[i] = vv;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {      // scalar tail
+        const long i = n4 * 4 + threadIdx.x;
+        const float gi = g[i] * coef;
+        float pv = p[i] * (1.0f - lr * wd);
+        const float mv = m[i] + (gi - m[i]) * (1.0f - b1);
+        const float vv = b2 * v[i] + (1.0f - b2) * gi * gi;
+        pv -= step_size * (mv / (sqrtf(vv) * inv_bc2_sqrt + eps));
+        p[i] = pv; m[i] = mv; v[i] = vv;
+    }
+}
+
 // 16-byte patchify: one thread per 4 channels of a grid node (C % 4 == 0); a node's C channels stay contiguous on both sides
 // IDX = unsigned (everything below 2^31 elements: the index arithmetic is five divisions per 16 bytes moved, and 64-bit ones cost four
 // times the 32-bit ones) or long
@@ -917,5 +1028,25 @@ extern "C" int gaot_adamw_apply_dev(float* p, const float* g, float* m, float* v
     hipLaunchKernelGGL(adamw_kernel, dim3(cap_blocks(n / 4 + 1, 256, 2048)), dim3(256), 0, ST(stream), p, g, m, v, (long)n, 0.f, 0.f,
                        0.f, 0.f, 0.f, step, hyper);
     GAOT_CHECK_LAUNCH("gaot_adamw_apply_dev");
+    return GAOT_OK;
+}
+
+extern "C" int gaot_grad_norm_dev(const float* g, int64_t n, float* partial, int32_t* ticket, const float* clip, float* step, int32_t ticked,
+                                  float* gstat, gaot_stream_t stream) {
+    GAOT_REQUIRE(g && partial && ticket && clip && step && gstat && n > 0 && aligned16(g),
+                 "grad_norm_dev: bad arguments (16-byte aligned g, partial[256], a zero ticket, clip[2], gstat[4])");
+    hipLaunchKernelGGL(grad_norm_kernel, dim3(grad_norm_blocks(n)), dim3(256), 0, ST(stream), g, (long)n, partial, ticket, clip, step, (int)ticked,
+                       gstat);
+    GAOT_CHECK_LAUNCH("gaot_grad_norm_dev");
+    return GAOT_OK;
+}
+
+extern "C" int gaot_adamw_apply_clipped_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, const float* step,
+                                            const float* gstat, const float* clip, gaot_stream_t stream) {
+    GAOT_REQUIRE(p && g && m && v && step && hyper && gstat && clip && n > 0, "adamw_apply_clipped_dev: bad arguments");
+    GAOT_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "adamw_apply_clipped_dev: flat buffers must be 16-byte aligned");
+    hipLaunchKernelGGL(adamw_clipped_kernel, dim3(cap_blocks(n / 4 + 1, 256, 2048)), dim3(256), 0, ST(stream), p, g, m, v, (long)n, step, hyper,
+                       gstat, clip);
+    GAOT_CHECK_LAUNCH("gaot_adamw_apply_clipped_dev");
     return GAOT_OK;
 }

@@ -169,11 +169,27 @@ class FlatAdamW(torch.optim.Optimizer):
 
     It IS a torch.optim.Optimizer with one param_group, so the reference's LR schedulers (optimizers.py:199-245) attach to
     it unchanged; lr / betas / eps / weight_decay are read by the kernel from a 5-float DEVICE buffer that `step()` refreshes
-    from `param_groups[0]` whenever they changed -- a captured (hipGraph) update follows the schedule without re-capture."""
+    from `param_groups[0]` whenever they changed -- a captured (hipGraph) update follows the schedule without re-capture.
 
-    def __init__(self, bucket: "FlatGradBucket", lr: float, weight_decay: float, betas=(0.9, 0.999), eps: float = 1e-8):
+    `max_grad_norm` / `skip_nonfinite` (both off by default: then nothing below exists and step() launches what it always did):
+    clipping by the global gradient norm with torch.nn.utils.clip_grad_norm_'s formula, and a guard that drops an update whose
+    gradient norm is not finite.  One more streaming pass over the gradient buffer (gaot_grad_norm_dev) leaves
+    {norm, coef, ok, skipped_total} in a DEVICE record; the update (gaot_adamw_apply_clipped_dev) multiplies the gradient by `coef`
+    in registers, or -- not ok, skipping on -- touches nothing, and the norm pass leaves the step counter where it stood before the
+    update.  No host read anywhere: both launches replay inside a hipGraph.  The gradient buffer is NOT rewritten: after the step
+    `bucket.flat` (and every param.grad view of it) still holds the UNCLIPPED gradient.  Whether the feature is on is fixed at
+    construction (it changes the captured launch set); `param_groups[0]["max_grad_norm"]` may move between steps like lr
+    (None or inf: no clipping).  `grad_norm`, `clip_coef`, `step_ok` are 0-dim device views (reading them does not synchronise
+    until their value is asked for); `skipped_steps` synchronises."""
+
+    def __init__(self, bucket: "FlatGradBucket", lr: float, weight_decay: float, betas=(0.9, 0.999), eps: float = 1e-8,
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
         self.bucket = bucket
-        super().__init__(bucket.model_order, dict(lr=float(lr), betas=tuple(betas), eps=float(eps), weight_decay=float(weight_decay)))
+        self.clipping = max_grad_norm is not None or bool(skip_nonfinite)
+        defaults = dict(lr=float(lr), betas=tuple(betas), eps=float(eps), weight_decay=float(weight_decay))
+        if self.clipping:
+            defaults.update(max_grad_norm=None if max_grad_norm is None else float(max_grad_norm), skip_nonfinite=bool(skip_nonfinite))
+        super().__init__(bucket.model_order, defaults)
         ps = bucket.params
         with torch.no_grad():       # same layout as the gradient bucket (aligned starts, fused groups back to back)
             self.flat_p = torch.zeros_like(bucket.flat)
@@ -186,6 +202,11 @@ class FlatAdamW(torch.optim.Optimizer):
         self.step_count = torch.zeros(1, dtype=torch.float32, device=self.flat_p.device)
         self.hyper = torch.zeros(5, dtype=torch.float32, device=self.flat_p.device)
         self._hyper_host = None
+        self.clip = self.gstat = None
+        if self.clipping:          # {max_norm, skip_nonfinite} and the record {norm, coef, ok, skipped_total}
+            self.clip = torch.zeros(2, dtype=torch.float32, device=self.flat_p.device)
+            self.gstat = torch.zeros(4, dtype=torch.float32, device=self.flat_p.device)
+            self._clip_host = None
         self.sync_hyper()
 
     # ---- hyper-parameters live in param_groups[0] (what schedulers write) and are mirrored to the device buffer
@@ -207,6 +228,22 @@ class FlatAdamW(torch.optim.Optimizer):
         if cur != self._hyper_host:
             self.hyper.copy_(torch.tensor(cur, dtype=torch.float32), non_blocking=False)
             self._hyper_host = cur
+        if self.clipping:
+            mx = g.get("max_grad_norm")
+            cur = (float("inf") if mx is None else float(mx), 1.0 if g.get("skip_nonfinite") else 0.0)
+            if cur != self._clip_host:
+                self.clip.copy_(torch.tensor(cur, dtype=torch.float32), non_blocking=False)
+                self._clip_host = cur
+
+    def _stat(self, i: int) -> torch.Tensor:
+        if self.gstat is None:
+            raise RuntimeError("FlatAdamW was built without max_grad_norm / skip_nonfinite: no gradient norm is taken")
+        return self.gstat[i]
+
+    grad_norm = property(lambda self: self._stat(0), doc="global gradient norm of the last step BEFORE clipping (0-dim device view)")
+    clip_coef = property(lambda self: self._stat(1), doc="factor the last update multiplied the gradient by (0-dim device view)")
+    step_ok = property(lambda self: self._stat(2), doc="1.0 if the last step's gradient norm was finite, else 0.0 (0-dim device view)")
+    skipped_steps = property(lambda self: int(self._stat(3).item()), doc="updates dropped so far (synchronises)")
 
     # ---- checkpoint compatibility with torch.optim.AdamW (what the reference's save_ckpt / load_ckpt move around,
     # trainer_utils.py:23-92 with optimizers.py:196): same state_dict layout, parameters indexed in model order
@@ -239,6 +276,10 @@ class FlatAdamW(torch.optim.Optimizer):
         self.betas = tuple(float(b) for b in g["betas"])
         if "initial_lr" in g:
             self._g()["initial_lr"] = g["initial_lr"]
+        if self.clipping:
+            for k in ("max_grad_norm", "skip_nonfinite"):
+                if k in g:
+                    self._g()[k] = g[k]
         steps = {float(st["step"]) for st in sd["state"].values()}
         if len(steps) > 1:
             raise ValueError("FlatAdamW.load_state_dict: per-parameter step counts differ; the flat update has one counter")
@@ -255,12 +296,26 @@ class FlatAdamW(torch.optim.Optimizer):
         self.bucket.clear()
 
     def step(self, closure=None, _sync: bool = True, ticked: bool = False):
-        """`ticked`: the step counter has already been advanced for this update (ops.mse_loss_and_grad(tick=self.step_count))"""
+        """`ticked`: the step counter has already been advanced for this update (ops.mse_loss_and_grad(tick=self.step_count)).
+        With clipping on: the norm pass, then the update scaled in registers -- `bucket.flat` is NOT rewritten and still holds the
+        unclipped gradient afterwards; a skipped update leaves the counter at its value from before this update."""
         from . import _lib as L
         from . import ops
         from .ops import _p, _stream
         if _sync:
             self.sync_hyper()
+        if self.clipping:
+            dev = self.flat_p.device
+            ws = ops._scratch("gradnorm", dev, lambda: (torch.empty(256, device=dev, dtype=torch.float32),
+                                                        torch.zeros(1, device=dev, dtype=torch.int32)), "FlatAdamW.step")
+            n = self.flat_p.numel()
+            L.check(L.load().gaot_grad_norm_dev(_p(self.bucket.flat), n, _p(ws[0]), _p(ws[1]), _p(self.clip), _p(self.step_count),
+                                                1 if ticked else 0, _p(self.gstat), _stream()), "gaot_grad_norm_dev")
+            L.check(L.load().gaot_adamw_apply_clipped_dev(_p(self.flat_p), _p(self.bucket.flat), _p(self.m), _p(self.v), n, _p(self.hyper),
+                                                          _p(self.step_count), _p(self.gstat), _p(self.clip), _stream()),
+                    "gaot_adamw_apply_clipped_dev")
+            ops.bump_weights_generation()
+            return
         fn = L.load().gaot_adamw_apply_dev if ticked else L.load().gaot_adamw_step_dev
         L.check(fn(_p(self.flat_p), _p(self.bucket.flat), _p(self.m), _p(self.v), self.flat_p.numel(),
                    _p(self.hyper), _p(self.step_count), _stream()), "gaot_adamw_step_dev")
@@ -298,9 +353,13 @@ class TrainStep:
     """One reference-trainer step on fixed shapes.  `static` holds everything forward() needs except pndata."""
 
     def __init__(self, model: torch.nn.Module, lr: float = 8e-4, weight_decay: float = 1e-5, use_graph: bool = True,
-                 group=None, staged: Optional[bool] = None, stage_groups=None):
+                 group=None, staged: Optional[bool] = None, stage_groups=None, max_grad_norm: Optional[float] = None,
+                 skip_nonfinite: bool = False):
         """`staged`: split the backward at the model's cut points and reduce each phase's gradient slice while the next phase
-        runs (default: whenever there is more than one rank and the model offers `backward_phases()`)."""
+        runs (default: whenever there is more than one rank and the model offers `backward_phases()`).
+        `max_grad_norm` / `skip_nonfinite`: clip by the global gradient norm / drop an update whose norm is not finite (FlatAdamW).
+        The norm is taken where the update is taken -- after every stage group's all-reduce has been waited for -- so every rank
+        reads the same averaged buffer and decides the same way without another collective."""
         self.model = model
         model.auto_graph = False          # this harness captures the whole step itself (autograph.py serves plain eager loops)
         self.group = group
@@ -336,9 +395,14 @@ class TrainStep:
         dev = self.bucket.flat.device
         on_gpu = dev.type == "cuda"
         if on_gpu:
-            self.opt = FlatAdamW(self.bucket, lr=lr, weight_decay=weight_decay)
+            self.opt = FlatAdamW(self.bucket, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
         else:           # CPU (gloo tests of the data-parallel plumbing): torch's own AdamW, parameters in MODEL order
             self.opt = torch.optim.AdamW(self.bucket.model_order, lr=lr, weight_decay=weight_decay)
+            if max_grad_norm is not None or skip_nonfinite:      # same keys, same place as FlatAdamW's: a schedule moves them alike
+                self.opt.param_groups[0].update(max_grad_norm=None if max_grad_norm is None else float(max_grad_norm),
+                                                skip_nonfinite=bool(skip_nonfinite))
+        self.clipping = max_grad_norm is not None or bool(skip_nonfinite)
+        self._cpu_stat = None if on_gpu or not self.clipping else {"norm": torch.zeros(()), "skipped": 0}
         # (per-step random neighbour sub-sampling, MAGNOConfig.sampling_strategy, is drawn on the device with a device-resident seed --
         # plan.DropPlan -- so a captured step draws a fresh subset on every replay)
         self.use_graph = use_graph and on_gpu
@@ -485,11 +549,39 @@ class TrainStep:
             for w in works:
                 if w is not None:
                     w.wait()
-        if self._ticked:
+        if self._cpu_stat is not None:
+            self._cpu_clipped_update()
+        elif self._ticked:
             self.opt.step(ticked=True)
         else:
             self.opt.step()
         return loss
+
+    def _cpu_clipped_update(self):
+        """the CPU branch's form of FlatAdamW's clipping: clip_grad_norm_ (which, unlike the device kernels, scales the gradient views in
+        place) and a host-side finite check; a skipped update leaves parameters, moments and torch's step counters alone"""
+        g = self.opt.param_groups[0]
+        mx = g.get("max_grad_norm")
+        norm = torch.nn.utils.clip_grad_norm_(self.bucket.model_order, float("inf") if mx is None else float(mx))
+        self._cpu_stat["norm"] = norm.detach()
+        if g.get("skip_nonfinite") and not bool(torch.isfinite(norm)):
+            self._cpu_stat["skipped"] += 1
+            return
+        self.opt.step()
+
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        """global norm of the (rank-averaged) gradient of the last step, before clipping: a 0-dim tensor on the step's device"""
+        if not self.clipping:
+            raise RuntimeError("TrainStep was built without max_grad_norm / skip_nonfinite: no gradient norm is taken")
+        return self._cpu_stat["norm"] if self._cpu_stat is not None else self.opt.grad_norm
+
+    @property
+    def skipped_steps(self) -> int:
+        """updates dropped so far because their gradient norm was not finite (synchronises)"""
+        if not self.clipping:
+            return 0
+        return self._cpu_stat["skipped"] if self._cpu_stat is not None else self.opt.skipped_steps
 
     def bind(self, pndata: torch.Tensor, target: torch.Tensor, **forward_kwargs):
         """Fix the static buffers (shapes) of the step; later `step()` calls copy new data into them.
@@ -542,7 +634,9 @@ class TrainStep:
 
     def _capture_inner(self):
         # warm-up iterations must not advance training: snapshot weights + optimizer state, restore after capture
-        snap = [t.clone() for t in (self.opt.flat_p, self.opt.m, self.opt.v, self.opt.step_count)]
+        # (with clipping on also the norm record: the warm-up steps must leave no skip count behind)
+        state = [self.opt.flat_p, self.opt.m, self.opt.v, self.opt.step_count] + ([self.opt.gstat] if self.opt.clipping else [])
+        snap = [t.clone() for t in state]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):          # warm-up: builds GeometryPlans (they sync once), fills the allocator
@@ -572,7 +666,7 @@ class TrainStep:
             self._g_opt = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._g_opt, pool=pool, capture_error_mode="thread_local"):
                 self.opt.step(_sync=False, ticked=self._ticked)          # (graphs exist on the GPU only: FlatAdamW)
-        for dst, src in zip((self.opt.flat_p, self.opt.m, self.opt.v, self.opt.step_count), snap):
+        for dst, src in zip(state, snap):
             dst.copy_(src)
 
     def step(self, pndata: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None, xcoord: Optional[torch.Tensor] = None,

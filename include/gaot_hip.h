@@ -511,6 +511,23 @@ int gaot_adamw_step_dev(float* p, const float* g, float* m, float* v, int64_t n,
 /* The update alone, for a step counter something else has already advanced (gaot_mse_loss_fwd_bwd's `tick`): step is only read. */
 int gaot_adamw_apply_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, const float* step,
                          gaot_stream_t stream);
+/* Global gradient norm with the clip / skip decision taken on the device (torch.nn.utils.clip_grad_norm_ plus a non-finite guard,
+ * no host read: the launch replays inside a hipGraph).  g[n]: the flat gradient, 16-byte aligned, any n > 0 (the n % 4 tail is read
+ * scalar).  partial: 256 floats of scratch; ticket: one int32, ZERO before the first call (the kernel returns it to zero).
+ * clip[2] (DEVICE, read at run time) = {max_norm, skip_nonfinite}; max_norm = inf or <= 0 switches clipping off (coef = 1).
+ * gstat[4] (DEVICE, ZERO before the first call) receives {norm, coef, ok, skipped_total}: norm = ||g||_2 BEFORE clipping (sum of
+ * squares in fp32 per workgroup -- min(256, ceil(n / 4096)) workgroups of 256 threads, grid-strided 16-byte loads, one accumulator
+ * per thread -- then the partials in a fixed order in double: the bits depend on g and n alone); coef = min(1, max_norm / (norm + 1e-6));
+ * ok = isfinite(norm).  !ok with skip_nonfinite != 0 adds 1 to skipped_total and leaves step[0] at its value from before this
+ * update: `ticked` != 0 says the counter was already advanced for it (gaot_mse_loss_fwd_bwd's `tick`) and the tick is taken back;
+ * with ticked == 0 this launch advances the counter itself unless the update is skipped.  Follow with gaot_adamw_apply_clipped_dev. */
+int gaot_grad_norm_dev(const float* g, int64_t n, float* partial, int32_t* ticket, const float* clip, float* step, int32_t ticked,
+                       float* gstat, gaot_stream_t stream);
+/* gaot_adamw_apply_dev with every gradient entry multiplied by gstat[1] in registers (g itself is NOT rewritten: it still holds the
+ * unclipped gradient afterwards; coef = 1 gives gaot_adamw_apply_dev's bits).  gstat[2] == 0 with clip[1] != 0 (a non-finite norm,
+ * skipping on) leaves p, m and v untouched.  gstat / clip: what gaot_grad_norm_dev wrote / read on the same stream; step is only read. */
+int gaot_adamw_apply_clipped_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, const float* step,
+                                 const float* gstat, const float* clip, gaot_stream_t stream);
 /* patchify gaot.py:182-185,202-205 and its inverse gaot.py:224-231.  Latent grid H x W (x Dz; Dz = 0 for 2-D).
  * inverse = 0: in = grid[b, (h,w[,z]), c]  -> out = tokens[b, s, (p..., c)];  inverse = 1: the other way. */
 int gaot_patchify(const float* in, int32_t B, int32_t H, int32_t W, int32_t Dz, int32_t P, int32_t C,
