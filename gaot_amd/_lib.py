@@ -218,6 +218,11 @@ PROTOTYPES = {
     "gaot_rollout_input": (C.c_int, [_f, C.c_int32, _f, C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_int64, _f, _s]),
     "gaot_rollout_update": (C.c_int, [_f, _f, C.c_int32, _f, _f, _f, _f, C.c_float, C.c_int32, C.c_int64, _f, _s]),
     "gaot_patchify": (C.c_int, [_f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, C.c_int32, _f, _s]),
+    "gaot_rel_l1_errors_workspace": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
+    "gaot_rel_l1_errors": (C.c_int, [_f, C.c_int64, C.c_int64, _f, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _f, _f, _f, _f, _i,
+                                     C.c_int32, _f, _f, C.c_int64, _s]),
+    "gaot_median_mean": (C.c_int, [_f, C.c_int64, C.c_int32, C.c_int64, _f, _f, _s]),
+    "gaot_mse_loss_eval": (C.c_int, [_f, _f, C.c_int64, _f, _f, C.c_void_p, _s]),
 }
 
 _lib = None

@@ -225,7 +225,8 @@ class GAOT(nn.Module):
             if getattr(self, "_amax_lists", None) is None:
                 self._amax_lists = (list(self.parameters()),
                                     [g for m in self.modules() if hasattr(m, "fused_weight_groups") for g in m.fused_weight_groups()])
-            if not torch.is_grad_enabled() and ops.weights_current(self._amax_lists[0]):
+            # (ops.replayable_eval: an evaluation capture that outlives weight updates refreshes inside the graph, like a training capture)
+            if not torch.is_grad_enabled() and not ops.in_replayable_eval() and ops.weights_current(self._amax_lists[0]):
                 ops.begin_pass(keep_weights=True)
                 if torch.cuda.is_current_stream_capturing():
                     ops.pin_weight_table()

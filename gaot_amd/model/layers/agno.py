@@ -112,7 +112,8 @@ class AGNO(nn.Module):
             out = ops.nonlinear_transform(k, f3, plan, a, self.transform_type == "nonlinear")
         else:
             k = kernel_values
-            if k is None and not torch.is_grad_enabled():      # rollouts: k_e depends on geometry + weights only -> reuse across steps
+            reuse = not torch.is_grad_enabled() and not ops.in_replayable_eval()
+            if k is None and reuse:      # rollouts: k_e depends on geometry + weights only -> reuse across steps
                 key = (id(feat), plan.epoch, tuple(p._version for p in self.channel_mlp.parameters()), ops.weights_generation())
                 hit = getattr(self, "_infer_k", None)
                 if hit is not None and hit[0] == key and hit[1] is feat:
@@ -121,7 +122,7 @@ class AGNO(nn.Module):
                         self.__dict__.setdefault("_graph_keep", []).append(hit)
             if k is None:
                 k = self.channel_mlp(feat)                                   # [E, C]
-                if not torch.is_grad_enabled():
+                if reuse:
                     self._infer_k = (key, feat, k)
             if lift is not None:
                 return ops.gno_lift_transform(k, lift[0], lift[1], lift[2], plan, a)         # [B, Q, C]

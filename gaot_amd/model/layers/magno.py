@@ -130,9 +130,10 @@ class _MAGNOBase(nn.Module):
 
     def vx_static_ok(self, feats: torch.Tensor) -> bool:
         """training passes over caller-supplied per-sample graphs (static_trainer.py:180-202) without encoded kernel coordinates; everything
-        else (evaluation, rollouts, module-owned lists) keeps the composed unions of plan.merged_geometry"""
-        return (_plan.VX_STATIC and feats.is_cuda and torch.is_grad_enabled() and self.training and bool(self.precompute_edges)
-                and not self.node_embedding)
+        else (evaluation, rollouts, module-owned lists) keeps the composed unions of plan.merged_geometry -- but for an evaluation pass that
+        is captured for replay (ops.replayable_eval: trainer.EvalStep), which needs the static buffers as much as a training capture does"""
+        return (_plan.VX_STATIC and feats.is_cuda and ((torch.is_grad_enabled() and self.training) or ops.in_replayable_eval())
+                and bool(self.precompute_edges) and not self.node_embedding)
 
     def vx_unions(self, nbrs, src: torch.Tensor, dst: torch.Tensor, B: int, load: bool = True):
         """the static union of every scale for this batch, its table uploaded (not capturable).  src / dst: [B, n, d] or [n, d] coordinates.
@@ -214,7 +215,7 @@ class _MAGNOBase(nn.Module):
             # written in place by the layers that use them
             w_agno, w_geo = ops.split_cols(w, C, param=self.recovery.fcs[0].weight)
             key = None
-            if not torch.is_grad_enabled() and nb is neighbors:
+            if not torch.is_grad_enabled() and nb is neighbors and not ops.in_replayable_eval():
                 # inference (autoregressive rollouts): geometry and weights are fixed across steps -> keep the row bias
                 key = (id(nb), id(src_coord), src_coord._version, id(dst_coord), dst_coord._version,
                        tuple(p._version for p in self.geoembed.parameters()), self.recovery.fcs[0].weight._version,
@@ -284,7 +285,7 @@ class _MAGNOBase(nn.Module):
                         raise ValueError("vx mode needs the same number of source / query points in every sample of a batch")
                     mg.refresh()
                     pl, nbu = mg.plan, mg.neighbors
-                    if self.sampling_strategy is not None:
+                    if self.training and self.sampling_strategy is not None:
                         # drawn per edge / per row, so drawing on the union IS drawing per sample (magno.py:372-378); the statistics of the
                         # sub-sampled graph are standardised per sample (gemb.py:164-169) like the full graph's
                         pl = _plan.dropped_plan(mg.plan, self.sampling_strategy, self.max_neighbors, self.sample_ratio)

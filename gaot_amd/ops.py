@@ -1399,6 +1399,46 @@ def mse_loss(pred, target):
 
 
 
+def mse_loss_eval(pred, target, running: torch.Tensor):
+    """mse_loss() (the same bits, no autograd node) whose finishing launch also adds the batch loss into `running`: a device float64
+    pair {sum of losses, number of batches} (trainer.EvalStep: a validation loop without a host read per batch)"""
+    _dev(pred, target, running)
+    _f32(pred, target)
+    p, t = pred.detach().contiguous(), target.contiguous()
+    assert p.shape == t.shape, (p.shape, t.shape)
+    if running.dtype != torch.float64 or running.numel() != 2 or not running.is_contiguous():
+        raise TypeError("mse_loss_eval: `running` is a contiguous float64 tensor of two entries")
+    part = _scratch("mse_eval", p.device, lambda: torch.empty(256, device=p.device, dtype=torch.float32), "mse_loss_eval")
+    loss = torch.empty((), device=p.device, dtype=torch.float32)
+    L.check(L.load().gaot_mse_loss_eval(_p(p), _p(t), p.numel(), _p(part), _p(loss), _p(running), _stream()), "gaot_mse_loss_eval")
+    return loss
+
+
+# --------------------------------------------------------------------------------------------
+# An evaluation forward that is captured ONCE and replayed while training goes on moving the weights (trainer.EvalStep).  A plain
+# no_grad forward may keep what depends on the weights from one call to the next -- the magnitude words and fp16 planes of the previous
+# pass (GAOT._forward_eager), the AGNO kernel values, the geoembed row bias -- because its caches are keyed on the weights' versions; a
+# captured graph has no key to miss: whatever the capture reads from such a cache is baked in.  Inside `replayable_eval()` nothing
+# weight-derived is reused (everything is recomputed by launches that become part of the graph), and a vx batch runs over the static
+# padded unions that training captures use (plan.StaticUnion) instead of a union composed on the host.  No existing caller enters it.
+# --------------------------------------------------------------------------------------------
+_REPLAYABLE_EVAL = [0]
+
+
+class replayable_eval:
+    def __enter__(self):
+        _REPLAYABLE_EVAL[0] += 1
+        return self
+
+    def __exit__(self, et, ev, tb):
+        _REPLAYABLE_EVAL[0] -= 1
+        return False
+
+
+def in_replayable_eval() -> bool:
+    return _REPLAYABLE_EVAL[0] > 0
+
+
 def mse_loss_and_grad(pred, target, tick: Optional[torch.Tensor] = None):
     """(loss, d loss / d pred) of nn.MSELoss() for a unit seed in ONE launch (trainer.TrainStep: `pred.backward(dpred)` continues
     the backward pass; the loss carries no graph).  Same bits as mse_loss().  `tick`: an optimizer's device-resident step counter,

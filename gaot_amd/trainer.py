@@ -723,3 +723,161 @@ class TrainStep:
         from . import ops
         ops.bump_weights_generation()
         return self._loss
+
+
+class EvalStep:
+    """One validation step of the reference trainers on fixed shapes (static_trainer.py:204-265, sequential_trainer.py:243-320): the
+    forward in evaluation mode under no_grad plus the MSE loss, captured as ONE hipGraph; the loss is also added into a device-resident
+    running pair, so a validation loop reads the host once (`mean_loss()`).
+
+        ev = EvalStep(model)
+        ev.bind(pndata, target, **forward_kwargs)               # TrainStep.bind's rules, vx included
+        for batch in loader: ev.step(pndata, target)            # device scalar, no host wait
+        val = ev.mean_loss(); ev.reset()
+
+    The captured step stays valid while training moves the weights: everything weight-derived (magnitude words, fp16 planes, AGNO kernel
+    values, the geoembed row bias) is recomputed inside the graph (ops.replayable_eval), where a plain no_grad forward would keep the
+    previous pass's and a rollout capture pins them.  `n_captures` counts the captures made.  The model may belong to a TrainStep as
+    well (same parameter storage; `auto_graph` is left alone); its `training` flags are put back as they were found.  `step()` returns
+    the step's static loss buffer: read or clone it before the next step."""
+
+    MAX_GRAPH_SETS = 6      # vx: captured steps kept (one per combination of the unions' edge buckets), least recently used first out
+
+    def __init__(self, model: torch.nn.Module, use_graph: bool = True):
+        self.model = model
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("gaot_amd ops take device tensors only (no CPU fallback); EvalStep needs the model on the GPU")
+        self.use_graph = bool(use_graph)
+        self.n_captures = 0
+        self._running = torch.zeros(2, dtype=torch.float64, device=dev)      # {sum of batch losses, batches}
+        self._x = self._y = self._loss = self._pred = None
+        self._graph: Optional[torch.cuda.CUDAGraph] = None
+        self._kwargs: Dict = {}
+        self._vx = False
+        self._vx_unions = None
+        self._graph_sets: Dict = {}
+        self._scratch: Dict = {}      # this step's own loss partials (ops.scratch_owner)
+
+    @property
+    def prediction(self) -> torch.Tensor:
+        """the last step's prediction (the step's static buffer: feed it to gaot_amd.metrics before the next step)"""
+        return self._pred
+
+    def bind(self, pndata: torch.Tensor, target: torch.Tensor, **forward_kwargs):
+        """fix the static buffers (shapes) of the step; `step()` copies new data into them.  A vx binding (xcoord [B, N, d] with per-sample
+        `encoder_nbrs` / `decoder_nbrs`) makes the coordinates static too and lets the graphs change with every step, as TrainStep.bind does."""
+        from . import plan as P
+        self._x = pndata.clone()
+        self._y = target.clone()
+        self._kwargs = dict(forward_kwargs)
+        self._graph = self._loss = self._pred = None
+        self._graph_sets = {}
+        self._vx_unions = None
+        xc = forward_kwargs.get("xcoord")
+        enc, dec = getattr(self.model, "encoder", None), getattr(self.model, "decoder", None)
+        self._vx = bool(torch.is_tensor(xc) and xc.dim() == 3 and xc.is_cuda and forward_kwargs.get("encoder_nbrs") is not None
+                        and forward_kwargs.get("decoder_nbrs") is not None and forward_kwargs.get("query_coord") is None
+                        and all(hasattr(m, "vx_static_ok") for m in (enc, dec))
+                        and P.VX_STATIC and all(bool(m.precompute_edges) and not m.node_embedding for m in (enc, dec)))
+        if self._vx:
+            self._kwargs["xcoord"] = xc.detach().clone().contiguous()
+            self._kwargs["latent_tokens_coord"] = forward_kwargs["latent_tokens_coord"].detach().contiguous()
+
+    def _vx_load(self):
+        """upload this step's union tables (per scale, encoder and decoder) and pick the captured step of their buckets"""
+        kw = self._kwargs
+        B = self._x.shape[0]
+        enc = self.model.encoder.vx_unions(kw["encoder_nbrs"], kw["xcoord"], kw["latent_tokens_coord"], B)
+        dec = self.model.decoder.vx_unions(kw["decoder_nbrs"], kw["latent_tokens_coord"], kw["xcoord"], B)
+        self._vx_unions = (enc, dec)
+        key = tuple((u.uid, u.pending_raw) for u in enc + dec)
+        hit = self._graph_sets.pop(key, None)
+        if hit is None:
+            while len(self._graph_sets) >= self.MAX_GRAPH_SETS:
+                self._graph_sets.pop(next(iter(self._graph_sets)))
+            hit = {"graph": None, "loss": None, "pred": None, "unions": (enc, dec)}
+        self._graph_sets[key] = hit
+        return hit
+
+    def _forward_loss(self) -> torch.Tensor:
+        from . import ops
+        flags = [(m, m.training) for m in self.model.modules()]
+        self.model.eval()
+        try:
+            with torch.no_grad(), ops.replayable_eval():
+                if self._vx_unions is not None:       # vx: the tables were uploaded by _vx_load(); the forward only re-composes (capturable)
+                    self.model.encoder._vx_preloaded = (self._vx_unions[0], self._kwargs["encoder_nbrs"])
+                    self.model.decoder._vx_preloaded = (self._vx_unions[1], self._kwargs["decoder_nbrs"])
+                self._pred = self.model(pndata=self._x, **self._kwargs)
+                return ops.mse_loss_eval(self._pred, self._y, self._running)
+        finally:
+            for m, was in flags:
+                m.training = was
+
+    def _eager_step(self) -> torch.Tensor:
+        from . import ops
+        with ops.scratch_owner(self._scratch):
+            return self._forward_loss()
+
+    def _capture(self):
+        from . import ops
+        snap = self._running.clone()          # the warm-up passes are not batches of the caller's loop
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):          # warm-up: builds GeometryPlans (they sync once), allocates the scratch, fills the allocator
+            for _ in range(2):
+                self._eager_step()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with ops.scratch_owner(self._scratch):
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                self._loss = self._forward_loss()
+        # the weight table the capture built points at buffers no kernel has filled yet (capturing runs nothing): nobody may take it for current
+        ops.begin_pass()
+        self._running.copy_(snap)
+        self._graph = g
+        self.n_captures += 1
+
+    def step(self, pndata: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None, xcoord: Optional[torch.Tensor] = None,
+             encoder_nbrs=None, decoder_nbrs=None) -> torch.Tensor:
+        """one evaluation step on new fields and -- vx -- a new geometry; returns the batch loss as a 0-dim device tensor (no host wait)"""
+        if self._x is None:
+            raise RuntimeError("EvalStep.step: bind() first")
+        if pndata is not None:
+            self._x.copy_(pndata, non_blocking=True)
+        if target is not None:
+            self._y.copy_(target, non_blocking=True)
+        if xcoord is not None or encoder_nbrs is not None or decoder_nbrs is not None:
+            if not self._vx:
+                raise RuntimeError("EvalStep.step: a new geometry per step needs a vx binding (xcoord [B, N, d] with encoder_nbrs / decoder_nbrs, "
+                                   "no node_embedding); bind() again for another fixed geometry")
+            if xcoord is not None:
+                self._kwargs["xcoord"].copy_(xcoord, non_blocking=True)
+            if encoder_nbrs is not None:
+                self._kwargs["encoder_nbrs"] = encoder_nbrs
+            if decoder_nbrs is not None:
+                self._kwargs["decoder_nbrs"] = decoder_nbrs
+        gs = None
+        if self._vx:
+            gs = self._vx_load()
+            self._graph, self._loss, self._pred = gs["graph"], gs["loss"], gs["pred"]
+        if not self.use_graph:
+            return self._eager_step()
+        if self._graph is None:
+            self._capture()
+            if gs is not None:
+                gs.update(graph=self._graph, loss=self._loss, pred=self._pred)
+        self._graph.replay()
+        return self._loss
+
+    def mean_loss(self) -> float:
+        """mean of the batch losses since the last reset(): the validation loss of static_trainer.py:219-221.  The one synchronisation."""
+        total, count = self._running.tolist()
+        if count == 0:
+            raise RuntimeError("EvalStep.mean_loss: no step since the last reset()")
+        return total / count
+
+    def reset(self) -> None:
+        self._running.zero_()

@@ -646,6 +646,36 @@ int gaot_rollout_input(const float* state, int32_t U, const float* stat, int32_t
 int gaot_rollout_update(const float* pred, float* state, int32_t U, const float* u_mean, const float* u_std, const float* a_mean,
                         const float* a_std, float dt, int32_t mode, int64_t rows, float* den_out, gaot_stream_t stream);
 
+/* ---- evaluation (additions within ABI 10): the reference's test metric and a validation loss that needs no host read per batch.
+ *
+ * gaot_rel_l1_errors replaces compute_batch_errors (utils/metrics.py:23-58) and, with the affine, the denormalize_data in front of it
+ * (trainer_utils.py:145).  gtr / prd: logically [B, T, N, V] fp32, the inner [N, V] block contiguous, each tensor with its own ELEMENT
+ * strides of b and t (>= N * V; ignored where the extent is 1) -- so `y[:, -1:]` (sequential_trainer.py:433-434) and a step-major
+ * rollout slab go in without a copy.  V <= 32.  Per element, in fp32 with every operation rounded on its own: x = x * affine_a[v] +
+ * affine_b[v] (both NULL: skipped), then (x - mean[v]) / std[v] with a true division.  sum |g - p| and sum |g| per (b, v) over t and n
+ * are taken in float64: in registers per thread, in a fixed tree per workgroup, the workgroups' partials in a fixed order by a second
+ * launch -- no floating-point atomics; two calls give the same bits and nothing in the workspace is read before it was written.
+ * The variables of chunk c (chunk_of_var[v] == c, DEVICE int32[V]; values outside 0..C-1 are ignored) are added in index order and
+ *   err_out[b * ld_err + c] = (float)num / ((float)den + 1e-10f)                 (metrics.py:56), C <= 256, ld_err >= C.
+ * workspace: gaot_rel_l1_errors_workspace(B, T, N, V) FLOATS (0: bad arguments), 8-byte aligned.  Both tensors are read once, as
+ * 16-byte vectors over the flat [N * V] span where the bases and strides are multiples of 16 bytes, as scalars elsewhere; the grid
+ * follows the byte count (up to 2048 workgroups), not B. */
+int64_t gaot_rel_l1_errors_workspace(int64_t B, int64_t T, int64_t N, int32_t V);
+int gaot_rel_l1_errors(const float* gtr, int64_t gtr_stride_b, int64_t gtr_stride_t, const float* prd, int64_t prd_stride_b,
+                       int64_t prd_stride_t, int64_t B, int64_t T, int64_t N, int32_t V, const float* affine_a,
+                       const float* affine_b, const float* mean, const float* std_, const int32_t* chunk_of_var, int32_t C,
+                       float* workspace, float* err_out, int64_t ld_err, gaot_stream_t stream);
+/* compute_final_metric (utils/metrics.py:70-76) over errs [n, C] with row stride ld: median_out[c] = the LOWER median of column c, i.e.
+ * the element of rank (n - 1) / 2 -- what torch.median(dim=0) returns: a selection, bit-equal to an input element -- and metric_out[0] =
+ * the mean of the C medians (summed in double in index order, rounded once).  A NaN anywhere in a column makes its median, and the
+ * metric, NaN.  Selection by rank counting (entries that sort before an entry, ties by index): any n up to 2^31, O(n^2 C) comparisons,
+ * no workspace, deterministic. */
+int gaot_median_mean(const float* errs, int64_t n, int32_t C, int64_t ld, float* median_out, float* metric_out, gaot_stream_t stream);
+/* gaot_mse_loss_fwd (the same bits in loss[0]) whose finishing launch also adds the batch loss into running = {sum of losses, number of
+ * batches}, two DEVICE doubles the caller zeroes: a validation loop reads the host once, at its end (static_trainer.py:204-265). */
+int gaot_mse_loss_eval(const float* pred, const float* target, int64_t n, float* partial, float* loss, double* running,
+                       gaot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
