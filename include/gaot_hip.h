@@ -676,6 +676,36 @@ int gaot_median_mean(const float* errs, int64_t n, int32_t C, int64_t ld, float*
 int gaot_mse_loss_eval(const float* pred, const float* target, int64_t n, float* partial, float* loss, double* running,
                        gaot_stream_t stream);
 
+/* ---- sequential training batches composed on the device (additions within ABI 10): the reference's DynamicPairDataset item
+ * (datasets/data_utils.py:162-235) and TestDataset item (:355-402) for a DEVICE list of indices, one launch each, from trajectories that
+ * stay resident: u [S, T, N, U] and, optionally (Cc > 0), c [S, T, N, Cc], fp32, contiguous.  Nothing about the batch but its shape is a
+ * launch argument: a captured step replays with new indices.  Every operation is rounded on its own in the reference's order (true
+ * divisions, no contraction): the outputs equal the reference's fp32 tensor expressions bit for bit.  Slab offsets are 64-bit; one
+ * item's [N, width] block must stay below 2^31 elements, S * P below 2^31, B <= 65535.
+ *
+ * gaot_seq_pairs_compose: idx[b] is a flat dataset index, sample = idx / P and pair = idx % P (:169-170); t_in / t_out (int32 [P]) are
+ * the pair's time indices, start_norm / diff_norm / diff (fp32 [P]) its two time features and its raw time difference.
+ *   x[b, n, :] = [(u_in - u_mean) / u_std, (c_in - c_mean) / c_std, start_norm[pair], diff_norm[pair]]       [B, N, U + Cc + n_time]
+ *                (c_mean = c_std = NULL: c as stored; n_time = 1: without the diff_norm column, and cond[b] = start_norm[pair] --
+ *                exactly x[..., :-1] and x[:, 0, -2:-1] of the n_time = 2 form, what sequential_trainer.py:192-198 feeds a
+ *                conditioned-norm model)
+ *   y[b, n, :] = mode 0 'output'  : (u_out - u_mean) / u_std                                                  [B, N, U]
+ *                mode 1 'residual': ((u_out - u_in) - a_mean) / a_std
+ *                mode 2 'time_der': (((u_out - u_in) / diff[pair]) - a_mean) / a_std
+ * gaot_seq_test_compose: idx[b] is a sample id, tidx (int32 [K + 1]) the time indices of a rollout.
+ *   x0[b, n, :] = [(u - u_mean) / u_std, (c - c_mean) / c_std, 0, 0] at tidx[0]                               [B, N, U + Cc + 2]
+ *   yseq[b, k]  = u[idx[b], tidx[k + 1]] as stored                                                            [B, K, N, U]
+ * An index outside its range is clamped and *status_flag |= 1 (idx) or |= 2 (a time index from t_in / t_out / tidx); the flag is only
+ * ever OR-ed into (the caller zeroes it); no read leaves the trajectories. */
+int gaot_seq_pairs_compose(const float* u, const float* c, int32_t S, int32_t T, int32_t N, int32_t U, int32_t Cc, const int32_t* t_in,
+                           const int32_t* t_out, const float* start_norm, const float* diff_norm, const float* diff, int32_t P,
+                           const float* u_mean, const float* u_std, const float* c_mean, const float* c_std, const float* a_mean,
+                           const float* a_std, int32_t mode, int32_t n_time, const int32_t* idx, int32_t B, float* x, float* y, float* cond,
+                           int32_t* status_flag, gaot_stream_t stream);
+int gaot_seq_test_compose(const float* u, const float* c, int32_t S, int32_t T, int32_t N, int32_t U, int32_t Cc, const float* u_mean,
+                          const float* u_std, const float* c_mean, const float* c_std, const int32_t* idx, int32_t B, const int32_t* tidx,
+                          int32_t K, float* x0, float* yseq, int32_t* status_flag, gaot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
