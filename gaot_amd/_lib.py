@@ -90,6 +90,7 @@ PROTOTYPES = {
     "gaot_debug_set_gemm_pieces": (C.c_int, [C.c_int]),
     "gaot_gemm_path": (C.c_int, [C.POINTER(GemmDesc)]),
     "gaot_gemm_slab_count": (C.c_int32, [C.c_int32, C.c_int32]),
+    "gaot_debug_gemm_plan": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(C.c_int32)]),
     "gaot_absmax_grouped": (C.c_int, [C.POINTER(AbsmaxItem), C.c_int32, _s]),
     "gaot_split_f16_planes_grouped": (C.c_int, [C.POINTER(F16PlanesItem), C.c_int32, _s]),
     "gaot_debug_set_gemm_planes": (C.c_int, [C.c_int]),

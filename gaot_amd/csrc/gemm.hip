@@ -12,7 +12,7 @@
 //    single-buffer staging (next k-tile's global loads in flight under 16*TM*TN MFMAs).
 //  * workgroup ids are remapped so that one XCD (private L2) owns whole row-panels of A.
 #include "gemm_common.h"
-
+#include "gemm_plan.h"
 namespace gaot {
 
 constexpr int BK = 32;
@@ -337,52 +337,35 @@ static int launch_cfg(GemmArgs& a, bool ak, bool bk, bool vec, hipStream_t st) {
 
 using namespace gaot;
 
-static thread_local int g_last_path = 0;   // 1 = MFMA tile kernel, 2 = skinny VALU path (for the bench's roofline accounting)
+static_assert(GEMM_BK == BK && GEMM_ACT_SWIGLU == GAOT_ACT_SWIGLU, "gemm_plan.h repeats the kernels' k-tile and one act code");
+
+static thread_local int g_last_path = 0;   // GemmPlan::path of the calling thread's last product (for the bench's roofline accounting)
 extern "C" int gaot_debug_last_gemm_path(void) { return g_last_path; }
-static int g_use_glds = 1;   // eligible products run on the LDS-direct kernels (gemm_glds.hip); 0 = register-staged only
+static GemmSwitches g_sw;                  // the kernel-selection switches (gemm_plan.h); every setter below decodes its argument into it
 namespace gaot { void set_glds_stages(int n); }
 // on: 0 = register-staged kernels only, 1 = LDS-direct with the default 2-stage ring, 3 = LDS-direct with a 3-stage ring,
-// 4 = + split-bf16 tiles by heuristic (DEFAULT: +5 % on the GAOT step, same-box A/B on two boxes),
-// 5 = split-bf16 wherever eligible, 6 = split-bf16 for the SwiGLU-gate product only.
-static int g_split_bm256 = 0;    // 1: 256x128 (8-wave) split tiles when they still fill the chip, 2: wherever M >= 256 (tuning)
-static int g_use_split = 1;  // 1: eligible products run on the split-bf16 kernel (gemm_split.hip) per the heuristic; 2: always when eligible
+// 4 .. 9 = + the split tiles, 3 + SplitTiles (4, by heuristic, is the DEFAULT), 10 / 11 = as 4 / 5 with the 256x128 tiles (Tall256)
 extern "C" int gaot_debug_set_gemm_glds(int on) {
-    const int old = g_use_split ? 3 + g_use_split : g_use_glds;
-    g_use_glds = on != 0; g_use_split = on == 4 ? 1 : (on == 5 ? 2 : (on == 6 ? 3 : (on == 7 ? 4 : (on == 8 ? 5 : (on == 9 ? 6 : 0)))));   // 6: SwiGLU product only, 7: 64-row tiles wherever eligible, 8: as 4 without the 64-row tiles
-    g_split_bm256 = on == 10 ? 1 : (on == 11 ? 2 : 0);
-    if (on == 10) g_use_split = 1;
-    if (on == 11) g_use_split = 2;
+    const int old = g_sw.split != SplitTiles::Off ? 3 + (int)g_sw.split : (int)g_sw.glds;
+    g_sw.glds = on != 0;
+    g_sw.split = on >= 4 && on <= 9 ? (SplitTiles)(on - 3) : (on == 10 ? SplitTiles::Heuristic : (on == 11 ? SplitTiles::Everywhere : SplitTiles::Off));
+    g_sw.tall256 = on == 10 ? Tall256::WhileFull : (on == 11 ? Tall256::Everywhere : Tall256::Off);
     gaot::set_glds_stages(on == 3 ? 3 : 2);
     return old;
 }
-// precision override of the split tiles: 0 (default) = every call's own gaot_gemm_desc.pieces; 1 = operands rounded to bf16, one piece
-// product (bench `--dtype bf16` only); 2 / 3 = forced for A/B runs
-static int g_split_pieces = 3, g_split_pieces_forced = 0;
-extern "C" int gaot_debug_set_gemm_pieces(int n) {
-    const int old = g_split_pieces_forced ? g_split_pieces : 0;
-    g_split_pieces_forced = (n >= 1 && n <= 3); g_split_pieces = g_split_pieces_forced ? n : 3;
-    return old;
-}
-int gaot_forced_pieces() { return g_split_pieces_forced ? g_split_pieces : 0; }
-
-static int g_use_ad = 1;         // all-DMA fp16-piece tiles: 0 off, 1 per the heuristic, 2 / 3: 64- / 128-row tiles wherever eligible (A/B switch)
-extern "C" int gaot_debug_set_gemm_ad(int on) { const int old = g_use_ad; g_use_ad = on; return old; }
-static int g_ad_flush = 1;      // [r6] unsplit reductions of 1 025 .. 2 048 on the 64 x 64 all-DMA tiles with the in-kernel flush (gemm_ad.hip FL); 0 = off (K slabs as before)
-extern "C" int gaot_debug_set_gemm_ad_flush(int on) { const int old = g_ad_flush; if (on >= 0) g_ad_flush = on; return old; }      // (on < 0: query)
-static int g_ad_narrow = 5;     // 64 x 64 all-DMA tiles (A/B switch, bits): 1 = half-filled launches of outputs two tiles wide (default), 2 = also N <= 256, K <= 256 at full launches, 4 = also outputs THREE tiles wide (4 096 tokens x 384: the 3-D configuration's o_proj-shaped products, which fell to the fp32-MFMA tiles; default), 8 = K slabs of such products too (4 096 x 384 x 1 152 in two slabs: C5 5.20 -> 5.27 ms same-box, tools/c45_ab.py 5 13: off), 16 = the concatenated-input (A2) product of the skip block too (C4 1.498 -> 1.500, C5 5.12 -> 5.09: nothing: off)
-extern "C" int gaot_debug_set_gemm_ad_narrow(int on) { const int old = g_ad_narrow; g_ad_narrow = on; return old; }
-static int g_use_planes = 1;     // 0: ignore gaot_gemm_desc.b_planes (A/B switch)
+extern "C" int gaot_debug_set_gemm_pieces(int n) { const int old = g_sw.forced_pieces; g_sw.forced_pieces = (n >= 1 && n <= 3) ? n : 0; return old; }
+extern "C" int gaot_debug_set_gemm_ad(int on) { const int old = (int)g_sw.ad; g_sw.ad = (AdTiles)on; return old; }
+extern "C" int gaot_debug_set_gemm_ad_flush(int on) { const int old = g_sw.ad_flush; if (on >= 0) g_sw.ad_flush = on != 0; return old; }      // (on < 0: query)
+extern "C" int gaot_debug_set_gemm_ad_narrow(int on) { const int old = g_sw.ad_narrow; g_sw.ad_narrow = on; return old; }
+extern "C" int gaot_debug_set_gemm_planes(int on) { const int old = g_sw.planes; g_sw.planes = on != 0; return old; }
+extern "C" int gaot_debug_set_gemm_tile(int cfg) { const int old = g_sw.tile; g_sw.tile = cfg; return old; }
 extern "C" unsigned gaot_debug_split_redo_count(int reset) { return gaot::split_redo_count(reset != 0) + gaot::ad_redo_count(reset != 0); }
-extern "C" int gaot_debug_set_gemm_planes(int on) { const int old = g_use_planes; g_use_planes = on; return old; }
 static int g_ablate = 0;
 extern "C" int gaot_debug_set_gemm_ablate(int bits) { const int old = g_ablate; g_ablate = bits; return old; }
 static int g_aux_prefetch = 1;   // vector epilogues of the acts that read aux_in: 1 = a band's aux vectors issued together ahead of its LDS transpose, 0 = pass by pass (A/B switch; bit-identical)
 extern "C" int gaot_debug_set_gemm_aux_prefetch(int on) { const int old = g_aux_prefetch; g_aux_prefetch = on ? 1 : 0; return old; }
-static int g_tile_override = 0;   // tuning hook: 0 = heuristic, 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 128x32
-extern "C" int gaot_debug_set_gemm_tile(int cfg) { const int old = g_tile_override; g_tile_override = cfg; return old; }
 
-// dry: only decide which kernel family would serve the product (g_last_path), launch nothing
-static int gemm_run(const gaot_gemm_desc* d, gaot_stream_t stream, const bool dry) {
+static int gemm_validate(const gaot_gemm_desc* d) {
     GAOT_REQUIRE(d != nullptr, "gemm: null descriptor");
     GAOT_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "gemm: M,N,K must be positive (got %d,%d,%d)", d->M, d->N, d->K);
     GAOT_REQUIRE(d->A && d->B && (d->C || d->raw_slabs), "gemm: A, B, C must be non-null");
@@ -407,17 +390,52 @@ static int gemm_run(const gaot_gemm_desc* d, gaot_stream_t stream, const bool dr
     if (d->rowbias) GAOT_REQUIRE(d->rowbias_period > 0, "gemm: rowbias needs rowbias_period > 0");
     if (d->A2) GAOT_REQUIRE(d->k_split > 0 && d->k_split < d->K && d->k_split % BK == 0,
                             "gemm: A2 needs 0 < k_split < K and k_split %% %d == 0 (got %d)", BK, d->k_split);
-    const int nkt = cdiv(d->K, BK);
-    int split = d->split_k > 1 ? d->split_k : 1;
-    if (split > nkt) split = nkt;
-    if (split > 1) GAOT_REQUIRE(d->workspace != nullptr, "gemm: split_k > 1 needs a workspace");
+    if (gemm_slab_count(d->K, d->split_k) > 1) GAOT_REQUIRE(d->workspace != nullptr, "gemm: split_k > 1 needs a workspace");
     if (d->colsum) GAOT_REQUIRE(d->a_kmajor == 0 && d->A2 == nullptr, "gemm: colsum needs an m-major A operand (a_kmajor = 0)");
 
     GAOT_REQUIRE(d->pieces == 0 || (d->pieces >= 2 && d->pieces <= 4), "gemm: pieces must be 0 / 3 (three bf16 pieces), 4 (two fp16 pieces) or 2 (two bf16 pieces), got %d", d->pieces);
     GAOT_REQUIRE(d->pieces != 4 || (d->a_absmax && d->b_absmax && (!d->A2 || d->a2_absmax)), "gemm: pieces = 4 (fp16 pieces) needs a_absmax and b_absmax (and a2_absmax with A2)");
+    return GAOT_OK;
+}
+
+// what plan_gemm reads of a valid descriptor: looks at the pointers (present? aligned?), never through them
+static GemmFacts gemm_facts(const gaot_gemm_desc* d) {
+    auto ok4 = [](const void* ptr, long ld) { return ptr == nullptr || (aligned16(ptr) && ld % 4 == 0); };
+    GemmFacts f{};
+    f.M = d->M; f.N = d->N; f.K = d->K;
+    f.a_kmajor = d->a_kmajor != 0; f.b_kmajor = d->b_kmajor != 0;
+    f.act = d->act;
+    f.split_k = d->split_k; f.has_workspace = d->workspace != nullptr; f.raw_slabs = d->raw_slabs != 0;
+    f.has_colsum = d->colsum != nullptr;
+    f.has_a2 = d->A2 != nullptr; f.k_split = d->k_split;
+    // 16-byte vector path: contiguous extents and leading dims multiples of 4 floats, bases 16B aligned
+    f.vec = aligned16(d->A) && aligned16(d->B) && (d->lda % 4 == 0) && (d->ldb % 4 == 0) &&
+            (f.a_kmajor ? (d->K % 4 == 0) : (d->M % 4 == 0)) && (f.b_kmajor ? (d->K % 4 == 0) : (d->N % 4 == 0));
+    if (d->A2) f.vec = f.vec && aligned16(d->A2) && (d->lda2 % 4 == 0) && ((d->K - d->k_split) % 4 == 0);
+    f.vec_epi = (d->N % 4 == 0) && aligned16(d->C) && (d->ldc % 4 == 0) && ok4(d->bias, 4) && ok4(d->rowbias, d->ld_rowbias) &&
+                ok4(d->aux_in, d->ld_aux) && ok4(d->aux_out, d->ld_aux) && ok4(d->residual, d->ldr) && ok4(d->workspace, 4);
+    f.plain_epi = !d->bias && !d->rowbias && !d->rowscale && !d->aux_out && d->act == GAOT_ACT_NONE && ok4(d->residual, d->ldr) &&
+                  d->N % 4 == 0 && d->ldc % 4 == 0 && aligned16(d->C) && aligned16(d->workspace);
     // the debug override (1: `--dtype bf16` bench variant; 2 / 3 forced for A/B runs) wins over the call's own precision
-    int pieces = g_split_pieces_forced ? g_split_pieces : (d->pieces == 2 ? 2 : (d->pieces == 4 ? 4 : 3));
-    if (pieces >= 4 && !(d->a_absmax && d->b_absmax)) pieces = 3;
+    f.pieces = g_sw.forced_pieces ? g_sw.forced_pieces : (d->pieces == 2 ? 2 : (d->pieces == 4 ? 4 : 3));
+    if (f.pieces >= 4 && !(d->a_absmax && d->b_absmax)) f.pieces = 3;
+    // B pre-split into fp16 planes (weights, once per pass): only the split tiles with fp16 pieces read them
+    f.planes_offered = d->b_planes != nullptr;
+    f.planes_usable = f.pieces >= 4 && f.planes_offered && g_sw.planes && aligned16(d->b_planes) && d->ld_bplanes % 8 == 0 && d->b_plane_stride == 16 && d->K % 16 == 0;
+    return f;
+}
+
+// the register-staged configuration `cfg` of gemm_plan.h's CFG_TILES
+static void launch_cfg_tile(GemmArgs& a, int cfg, bool ak, bool bk, bool vec, hipStream_t st) {
+#define GAOT_CFG(i) case i: launch_cfg<CFG_TILES[i].bm, CFG_TILES[i].bn, CFG_TILES[i].waves_m, CFG_TILES[i].waves>(a, ak, bk, vec, st); break
+    switch (cfg) { GAOT_CFG(1); GAOT_CFG(2); GAOT_CFG(3); GAOT_CFG(4); GAOT_CFG(5); GAOT_CFG(6); }
+#undef GAOT_CFG
+}
+
+static int gemm_run(const gaot_gemm_desc* d, gaot_stream_t stream) {
+    if (int rc = gemm_validate(d)) return rc;
+    const GemmFacts f = gemm_facts(d);
+    const GemmPlan pl = plan_gemm(f, g_sw);
 
     GemmArgs a;
     a.M = d->M; a.N = d->N; a.K = d->K;
@@ -426,193 +444,62 @@ static int gemm_run(const gaot_gemm_desc* d, gaot_stream_t stream, const bool dr
     a.bias = d->bias; a.rowbias = d->rowbias; a.rb_period = d->rowbias_period; a.ld_rb = d->ld_rowbias;
     a.rowscale = d->rowscale; a.act = d->act; a.aux_in = d->aux_in; a.aux_out = d->aux_out; a.ld_aux = d->ld_aux;
     a.residual = d->residual; a.ldr = d->ldr;
-    a.split_k = split; a.ktiles_per_split = cdiv(nkt, split); a.ws = d->workspace;
+    a.split_k = pl.split_k; a.ktiles_per_split = pl.ktiles_per_split; a.ws = d->workspace;
     a.colsum = d->colsum;
     a.ablate = g_ablate;
     a.aux_pf = g_aux_prefetch;
-    a.a_amax = pieces >= 4 ? d->a_absmax : nullptr; a.b_amax = pieces >= 4 ? d->b_absmax : nullptr; a.c_amax = d->c_absmax;
-    a.a2_amax = pieces >= 4 ? d->a2_absmax : nullptr;
-    // B pre-split into fp16 planes (weights, once per pass): only the split tiles with fp16 pieces read them
+    a.a_amax = f.pieces >= 4 ? d->a_absmax : nullptr; a.b_amax = f.pieces >= 4 ? d->b_absmax : nullptr; a.c_amax = d->c_absmax;
+    a.a2_amax = f.pieces >= 4 ? d->a2_absmax : nullptr;
     a.Bpl = nullptr; a.ld_bpl = 0; a.bpl_stride = 0; a.bpl_flag = 0;
-    if (pieces >= 4 && d->b_planes != nullptr && g_use_planes && aligned16(d->b_planes) && d->ld_bplanes % 8 == 0 && d->b_plane_stride == 16 &&
-        d->K % 16 == 0) {
-        a.Bpl = reinterpret_cast<const unsigned short*>(d->b_planes); a.ld_bpl = d->ld_bplanes; a.bpl_stride = d->b_plane_stride;
-    }
-    {
-        auto ok4 = [](const void* ptr, long ld) { return ptr == nullptr || (aligned16(ptr) && ld % 4 == 0); };
-        a.vec_epi = (a.N % 4 == 0) && aligned16(a.C) && (a.ldc % 4 == 0) && ok4(a.bias, 4) && ok4(a.rowbias, a.ld_rb) &&
-                    ok4(a.aux_in, a.ld_aux) && ok4(a.aux_out, a.ld_aux) && ok4(a.residual, a.ldr) && ok4(a.ws, 4);
-    }
-    a.split_k = cdiv(nkt, a.ktiles_per_split);  // no empty splits
-    const bool raw = d->raw_slabs != 0;
-    if (raw) {
+    if (f.planes_usable) { a.Bpl = reinterpret_cast<const unsigned short*>(d->b_planes); a.ld_bpl = d->ld_bplanes; a.bpl_stride = d->b_plane_stride; }
+    a.vec_epi = pl.vec_epi;
+    if (f.raw_slabs) {
         a.c_amax = nullptr;
-        if (a.split_k <= 1) { a.C = a.ws; a.ldc = a.N; a.vec_epi = 1; }      // a reduction too short to cut: the product itself is slab 0
-        else if (a.C == nullptr) a.C = a.ws;                                  // (never written)
+        if (a.split_k <= 1) { a.C = a.ws; a.ldc = a.N; }      // a reduction too short to cut: the product itself is slab 0
+        else if (a.C == nullptr) a.C = a.ws;                  // (never written)
     }
-
-    const bool ak = d->a_kmajor != 0, bk = d->b_kmajor != 0;
-    // 16-byte vector path: contiguous extents and leading dims multiples of 4 floats, bases 16B aligned
-    bool vec = aligned16(d->A) && aligned16(d->B) && (d->lda % 4 == 0) && (d->ldb % 4 == 0);
-    vec = vec && (ak ? (d->K % 4 == 0) : (d->M % 4 == 0)) && (bk ? (d->K % 4 == 0) : (d->N % 4 == 0));
-    if (d->A2) vec = vec && aligned16(d->A2) && (d->lda2 % 4 == 0) && ((d->K - d->k_split) % 4 == 0);
 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (a.act == GAOT_ACT_SWIGLU) {          // only the LDS-staged kernels lay the gate's bands out
-        const long nb128 = (long)cdiv(a.M, 128) * cdiv(a.N, 128);
-        a.vec_epi = 1;
-        if (g_use_split == 2 || (g_use_split && nb128 >= 256)) {
-            g_last_path = 3;
-            if (dry) return GAOT_OK;
-            const bool big = a.M >= 256 && (g_split_bm256 == 2 || (g_split_bm256 == 1 && nb128 >= 500));
-            launch_split(a, ak, bk, st, big && pieces != 1 ? 256 : 128, pieces);
-        }
-        else { g_last_path = 1; if (dry) return GAOT_OK; launch_glds(a, ak, bk, nb128 >= 512 ? 1 : ((long)cdiv(a.M, 128) * cdiv(a.N, 64) >= 512 ? 2 : 3), st); }
-        GAOT_CHECK_LAUNCH("gaot_gemm_f32(swiglu)");
-        return GAOT_OK;
+    g_last_path = pl.path;
+    switch (pl.family) {
+        case GemmFamily::SkinnyTN: case GemmFamily::SkinnyK: case GemmFamily::SkinnyN: launch_skinny(a, pl.family, f.b_kmajor, st); break;
+        case GemmFamily::Cfg:   launch_cfg_tile(a, pl.variant, f.a_kmajor, f.b_kmajor, f.vec, st); break;
+        case GemmFamily::Glds:  launch_glds(a, f.a_kmajor, f.b_kmajor, pl.variant, st); break;
+        case GemmFamily::Split: launch_split(a, f.a_kmajor, f.b_kmajor, st, pl.variant, f.pieces); break;
+        case GemmFamily::Ad:    launch_ad(a, f.b_kmajor, st, pl.tile_rows, pl.tile_cols); break;
     }
-    if (g_tile_override == 0 && !raw && dry && skinny_would(a, ak, bk)) { g_last_path = 2; return GAOT_OK; }
-    // kernels without the vector epilogue do not publish C's magnitude word themselves: one absmax launch over C as stored
-    auto publish_after = [&]() -> int {
-        if (d->c_absmax == nullptr) return GAOT_OK;
+    GAOT_CHECK_LAUNCH("gaot_gemm_f32");
+    if (pl.reduce == GemmReduce::Vector) {
+        const long nb = cdiv((long)a.M * a.N / 4, 64) + (a.colsum ? cdiv(a.M, 64) : 0);
+        hipLaunchKernelGGL(splitk_reduce_vec_kernel, dim3((unsigned)nb), dim3(256), 0, st, a);
+    } else if (pl.reduce == GemmReduce::Scalar) {
+        int nb = cdiv((long)a.M * a.N, 256);
+        if (nb > 2048) nb = 2048;
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nb), dim3(256), 0, st, a);
+    }
+    if (pl.reduce != GemmReduce::None) GAOT_CHECK_LAUNCH("gaot_gemm_f32(split-k reduce)");
+    if (pl.publish_after && d->c_absmax != nullptr) {          // one absmax launch over C as stored
         const int32_t cols = a.act == GAOT_ACT_SWIGLU_BWD ? 2 * a.N : a.N;
         gaot_absmax_item it = {a.C, (int64_t)a.ldc, a.M, cols, d->c_absmax};
         return gaot_absmax_grouped(&it, 1, stream);
-    };
-    if (g_tile_override == 0 && !raw && !dry && launch_skinny(a, ak, bk, st)) {
-        g_last_path = 2;
-        GAOT_CHECK_LAUNCH("gaot_gemm_f32(skinny)");
-        return publish_after();
     }
-    g_last_path = 1;
-    // tile choice: the largest tile that still gives every CU (256) a workgroup; skinny N gets a 128x32 tile
-    const long z = a.split_k;
-    auto blocks = [&](int bm, int bn) { return (long)cdiv(a.M, bm) * cdiv(a.N, bn) * z; };
-    (void)z;
-    const bool glds_ok = g_use_glds && vec && a.vec_epi && a.K % 32 == 0 && a.M >= 4 && a.N >= 4;
-    // the bf16 MFMA does not round its fp32 accumulator to nearest: same-signed increments drift (4096^3 with positive
-    // operands: 1.1e-5 relative against 8e-7 on the fp32 MFMA, tools/acc_bias.py), so one workgroup accumulates at most 1 024
-    // values of k on that pipe; longer reductions either arrive split (the slabs are summed on the vector pipe) or stay on the
-    // fp32-MFMA tiles
-    const long k_per_wg = a.split_k > 1 ? (long)a.ktiles_per_split * 32 : a.K;
-    // [r6] unsplit reductions of 1 025 .. 2 048 on the 64 x 64 all-DMA tiles, which flush their accumulators every 1 024 values of k in the
-    // kernel (gemm_ad.hip FL): the narrow outputs whose K slabs would not fill the split tiles and fell to the fp32-MFMA tiles (4 096 x 384 x
-    // 1 152, the 3-D configuration's q|k|v input gradient: two slabs of 39 us + a reduce)
-    const bool long_k = g_ad_flush && pieces == 4 && a.split_k <= 1 && a.K > 1024 && a.K <= 2048 && !raw;
-    const bool split_ok = g_use_split && g_use_split != 3 && glds_ok && (a.A2 == nullptr || (ak && a.k_split % 16 == 0)) && g_tile_override == 0 &&
-                          (k_per_wg <= 1024 || pieces == 1 || g_use_split != 1 || long_k);      // forced tuning modes bypass the cap
-    // measured (round 2, tools/gemm_bench.py sweeps): the 128x128 split-bf16 tiles win once they fill the chip (>= 256 workgroups
-    // counting split-K slabs) on outputs at least one tile wide; narrower / smaller products stay on the fp32 MFMA tiles
-    // two-piece products, outputs at most six 128-wide tiles across (N <= 768): the 64-row tiles win although the 128-row ones would
-    // fill the chip (8192 x 768 x 256 NT: 21.7 vs 24.2 us, NN x 512 x 256: 18.6 vs 19.5; N >= 1 024: the other way round)
-    const bool two_pl = pieces == 2 || pieces >= 4;       // two planes per operand in LDS
-    const bool prefer64 = split_ok && !long_k && g_use_split == 1 && two_pl && ak && cdiv(a.N, 128) <= 6 && blocks(64, 128) >= 250 && a.M >= 64 &&
-                          a.N >= 128 && a.split_k <= 1;
-    const bool split128 = split_ok && !long_k && g_use_split != 4 && !prefer64 &&
-                          (g_use_split == 2 || (blocks(128, 128) >= 250 && a.M >= 128 && a.N >= 128 && (long)cdiv(a.M, 128) * cdiv(a.N, 128) >= 8));
-    // outputs only a few 128-wide tiles across (N = 256): 64-row tiles double the workgroup count
-    // (with pre-split B planes an NN product stages B exactly like an NT one; with two-piece products the 64-row split tiles beat the
-    // fp32-MFMA tiles on the NN products too: 8192 x 256 x 768 37.4 -> 25.6 us, x 512 26.5 -> 19.0, x 256 15.5 -> 12.8, tools/gemm_modes_2p.py)
-    const bool split64 = split_ok && !long_k && !split128 && g_use_split != 5 && g_use_split != 2 &&
-                         (g_use_split == 4 || prefer64 || ((ak && (bk || a.Bpl != nullptr || g_use_split == 6 || two_pl)) && blocks(64, 128) >= 250 && a.M >= 64 && a.N >= 128 && a.split_k <= 1));   // measured: NT +6-14 %, NN +-0
-    // 64 x 64 all-DMA tiles (gaot_debug_set_gemm_ad_narrow, bits): (1, default) half-filled launches of outputs two tiles wide (4 096 tokens x
-    // 256: 128 workgroups of 64 rows, which fall to the fp32-MFMA tiles) get 256 workgroups -- tools/ad_bench.hip: 4096 x 256 x 256 in 8.3 us
-    // against ~15; same-box step A/B at the 4 096-token batch (tools/step_ab.py --c4, twice): 1.6486 -> 1.6249, 1.6481 -> 1.6234 ms, C2
-    // untouched (its launches are full).  (2, off) N <= 256 with K <= 256 at 8 192 rows: 11.9 -> 11.2 us alone, but C2 2.1499 -> 2.1663,
-    // 2.1399 -> 2.1705 ms per step.  Bit-identical to the other fp16-piece tiles in every test (tests/test_ops_gpu.py, tools/ad_stress.py);
-    // a product that (1) moves off the fp32-MFMA tiles is rounded as the fp16-piece family rounds (same error class, other last bits).
-    // (An earlier series of A/B runs looked inconsistent and twice ended at an unexplained loss: that was the host-side slot bookkeeping,
-    // DESIGN 7, not these tiles.)
-    const bool narrow_shape = g_use_ad == 1 && (g_ad_narrow & 1) && split_ok && !split128 && !split64 && pieces == 4 && ak && a.K % 32 == 0 && a.vec_epi &&
-                              (a.split_k <= 1 || ((g_ad_narrow & 8) && !raw)) && (a.A2 == nullptr || ((g_ad_narrow & 16) && a.k_split % 32 == 0)) && (cdiv(a.N, 128) == 2 || ((g_ad_narrow & 4) && cdiv(a.N, 128) == 3)) && blocks(64, 64) >= 128 && (long)cdiv(a.M, 64) * cdiv(a.N, 128) < 250 &&
-                              (a.split_k <= 1 ? a.K : cdiv(cdiv(a.K, 32), a.split_k) * 32) <= (long_k ? 2048 : 1024);          // (bit 8: K slabs of such a product too -- 4 096 x 384 x 1 152 in two slabs)
-    const bool ad_narrow = narrow_shape && (dry ? d->b_planes != nullptr : a.Bpl != nullptr);
-    // planes handed in but switched off (gaot_debug_set_gemm_planes(0)): the same tile family on the staged 64-row kernel, so that the
-    // switch changes where B's pieces come from and nothing else (products WITHOUT planes -- B an activation -- stay where they were)
-    const bool narrow_staged = narrow_shape && !long_k && !dry && a.Bpl == nullptr && d->b_planes != nullptr;
-    if (dry) { g_last_path = (split128 || split64 || ad_narrow) ? 3 : 1; return GAOT_OK; }
-    if (split128 || split64 || ad_narrow || narrow_staged) {
-        g_last_path = 3;
-        // 256x128 (8-wave) tiles: measured +3-7 % on the NT / TN products that still give ~200 workgroups, -2 % on NN
-        const bool big = split128 && a.M >= 512 && (g_split_bm256 == 2 || (g_split_bm256 == 1 && ak == bk && blocks(256, 128) >= 190));
-        // all-DMA tiles (gemm_ad.hip; tools/ad_bench.hip, same box, us staged -> all-DMA): outputs two tiles wide (N <= 256) on 64-row
-        // tiles: 8192 x 256 x 256 13.5 -> 11.8, x 768 26.7 -> 22.1, x 1024 32.8 -> 26.8; wider outputs on 64-row tiles while those fit
-        // one round of two workgroups per CU (the 4 096-token batches), else on 128-row ones while THOSE fit one round; what needs more
-        // rounds (8192 x 2048 x 256: 49 -> 51-54 us; x 768: 23.2 -> 26.8 on 64-row tiles) and the K-slab products (8192 x 256 x 2048 in
-        // two slabs: 42.9 -> 42.6) stay on the staged kernel -- there the output stores / the slab count decide.  Step level
-        // (tools/step_ab.py, same box): C2 2.3225 -> 2.2666 ms, C4-shaped 1.8169 -> 1.7888
-        // Re-checked with the epilogue's aux prefetch in (tools/bin/ad_bench swiglu, u from HBM): the SwiGLU-gradient product 8192 x 1024 x 256
-        // 39.8-43.0 us on the 128-row tiles (one round) against 42.3-42.6 on the 64-row ones (two rounds): the rule stays
-        const bool ad_ok = g_use_ad && pieces == 4 && a.Bpl != nullptr && ak && a.K % 32 == 0 && a.vec_epi && (a.A2 == nullptr || a.k_split % 32 == 0);
-        const bool ad64 = ad_ok && (g_use_ad == 2 || (a.split_k <= 1 && (cdiv(a.N, 128) <= 2 || blocks(64, 128) <= 512) && blocks(64, 128) >= 128));
-        const bool ad128 = ad_ok && !ad64 && !big && (g_use_ad == 3 || (a.split_k <= 1 && split128 && blocks(128, 128) <= 512));
-        if (ad_narrow) launch_ad(a, bk, st, 64, 64);
-        else if (ad64) launch_ad(a, bk, st, 64, ((g_ad_narrow & 2) && a.K <= 256 && cdiv(a.N, 128) <= 2) ? 64 : 128);      // (8192 x 256 x 256: 11.9 -> 11.2 us on 64 x 64 tiles)
-        else if (ad128) launch_ad(a, bk, st, 128);
-        else
-        launch_split(a, ak, bk, st, (split64 || narrow_staged) ? 64 : (big && pieces != 1 ? 256 : 128), pieces);
-    }
-    else if (glds_ok && g_tile_override >= 0 && g_tile_override <= 3) {
-        int tile = g_tile_override;
-        if (tile == 0) {      // from the on-box sweep (round 2, tools/gemm_bench.py; 2-stage ring)
-            if (!ak && !bk) tile = blocks(128, 128) >= 256 ? 1 : (blocks(128, 64) >= 256 && a.M >= 128 ? 2 : 3);
-            else if (blocks(128, 128) >= 512) tile = 1;
-            else if (blocks(128, 64) >= 512) tile = 2;
-            else tile = 3;
-        }
-        launch_glds(a, ak, bk, tile, st);
-    }
-    else if (g_tile_override == 1)      launch_cfg<128, 128, 2>(a, ak, bk, vec, st);
-    else if (g_tile_override == 2)      launch_cfg<128, 64, 2>(a, ak, bk, vec, st);
-    else if (g_tile_override == 3)      launch_cfg<64, 64, 2>(a, ak, bk, vec, st);
-    else if (g_tile_override == 4)      launch_cfg<128, 32, 4>(a, ak, bk, vec, st);
-    else if (g_tile_override == 5)      launch_cfg<128, 128, 2, 8>(a, ak, bk, vec, st);
-    else if (g_tile_override == 6)      launch_cfg<128, 64, 4, 8>(a, ak, bk, vec, st);
-    else if (a.N <= 32)                 launch_cfg<128, 32, 4>(a, ak, bk, vec, st);
-    // measured on MI355X (tools/gemm_bench.py): short reductions want SEVERAL block-waves in flight so that the
-    // load / MFMA / store phases of different workgroups overlap; big tiles only pay off on large outputs.
-    // transposed-A weight gradients (long reduction, split-K): 128x64 measured 10-17 % ahead of 64x64 once it fills the chip
-    else if (!ak && !bk && blocks(128, 64) >= 256 && a.M >= 128) launch_cfg<128, 64, 2>(a, ak, bk, vec, st);
-    else if (blocks(64, 64) <= 1536)    launch_cfg<64, 64, 2>(a, ak, bk, vec, st);
-    else if (blocks(128, 64) <= 3072)   launch_cfg<128, 64, 2>(a, ak, bk, vec, st);
-    else                                launch_cfg<128, 128, 2>(a, ak, bk, vec, st);
-    GAOT_CHECK_LAUNCH("gaot_gemm_f32");
-    if (a.split_k > 1 && !raw) {
-        const long total = (long)a.M * a.N;
-        const bool plain = !a.bias && !a.rowbias && !a.rowscale && !a.aux_out && a.act == GAOT_ACT_NONE &&
-                           (!a.residual || (aligned16(a.residual) && a.ldr % 4 == 0)) &&
-                           a.N % 4 == 0 && a.ldc % 4 == 0 && aligned16(a.C) && aligned16(a.ws);
-        if (plain) {
-            const long nb = cdiv(total / 4, 64) + (a.colsum ? cdiv(a.M, 64) : 0);
-            hipLaunchKernelGGL(splitk_reduce_vec_kernel, dim3((unsigned)nb), dim3(256), 0, st, a);
-        } else {
-            int nb = cdiv(total, 256);
-            if (nb > 2048) nb = 2048;
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nb), dim3(256), 0, st, a);
-        }
-        GAOT_CHECK_LAUNCH("gaot_gemm_f32(split-k reduce)");
-    }
-    else if (!a.vec_epi && !raw) return publish_after();
     return GAOT_OK;
 }
 
-extern "C" int32_t gaot_gemm_slab_count(int32_t K, int32_t split_k) {
-    const int nkt = cdiv(K > 0 ? K : 1, BK);
-    int split = split_k > 1 ? split_k : 1;
-    if (split > nkt) split = nkt;
-    return cdiv(nkt, cdiv(nkt, split));
-}
+extern "C" int32_t gaot_gemm_slab_count(int32_t K, int32_t split_k) { return gemm_slab_count(K > 0 ? K : 1, split_k); }
 
-
-extern "C" int gaot_gemm_f32(const gaot_gemm_desc* d, gaot_stream_t stream) { return gemm_run(d, stream, false); }
+extern "C" int gaot_gemm_f32(const gaot_gemm_desc* d, gaot_stream_t stream) { return gemm_run(d, stream); }
 // which kernel family WOULD serve this product (as gaot_debug_last_gemm_path: 1 fp32-MFMA tiles, 2 skinny, 3 split tiles on the
 // bf16 / fp16 matrix pipe); launches nothing.  Callers use it to decide whether the fp16-piece operands' absmax words are needed.
-extern "C" int gaot_gemm_path(const gaot_gemm_desc* d) {
-    const int keep = g_last_path;
-    const int rc = gemm_run(d, nullptr, true);
-    const int path = rc == GAOT_OK ? g_last_path : -1;
-    g_last_path = keep;
-    return path;
+extern "C" int gaot_gemm_path(const gaot_gemm_desc* d) { return gemm_validate(d) == GAOT_OK ? plan_gemm(gemm_facts(d), g_sw).path : -1; }
+// the whole plan of a product, as {path, family, tile_rows, tile_cols, variant, split_k, reduce, publish_after} (gemm_plan.h); launches nothing
+extern "C" int gaot_debug_gemm_plan(const gaot_gemm_desc* d, int32_t out[8]) {
+    GAOT_REQUIRE(out != nullptr, "gemm_plan: null output");
+    if (int rc = gemm_validate(d)) return rc;
+    const GemmPlan pl = plan_gemm(gemm_facts(d), g_sw);
+    const int32_t v[8] = {pl.path, (int32_t)pl.family, pl.tile_rows, pl.tile_cols, pl.variant, pl.split_k, (int32_t)pl.reduce, pl.publish_after};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return GAOT_OK;
 }
 
 // ---- grouped weight-gradient products (kernel: gemm_split.hip)
@@ -650,7 +537,7 @@ extern "C" int64_t gaot_gemm_tn_grouped_workspace(const gaot_wgrad_item* items, 
 
 extern "C" int gaot_gemm_tn_grouped(const gaot_wgrad_item* items, int32_t n, int32_t pieces, float* workspace, int32_t* counters, gaot_stream_t stream) {
     GAOT_REQUIRE(pieces == 0 || (pieces >= 2 && pieces <= 4), "gemm_tn_grouped: pieces must be 0 / 3, 4 (two fp16 pieces) or 2, got %d", pieces);
-    if (gaot_forced_pieces() >= 2) pieces = gaot_forced_pieces();
+    if (g_sw.forced_pieces >= 2) pieces = g_sw.forced_pieces;
     if (int rc = check_wgrad_items(items, n)) return rc;
     if (pieces >= 4) for (int i = 0; i < n; ++i) if (!items[i].g_absmax || !items[i].x_absmax) { pieces = 3; break; }
     int cnt = 0;

@@ -376,7 +376,7 @@ void launch_ad(GemmArgs& a, bool b_kmajor, hipStream_t st, int bm, int bn) {
     a.bpl_flag = b_kmajor ? 1 : 2;
     dim3 grid(a.tiles_m * a.tiles_n, 1, a.split_k > 1 ? a.split_k : 1), block(256);
     const long k_per_wg = a.split_k > 1 ? (long)a.ktiles_per_split * AD_BK : a.K;
-    if (bm == 64 && bn == 64 && k_per_wg > 1024) {          // (the dispatcher sends reductions past the cap here only: gemm.hip ad_narrow)
+    if (bm == 64 && bn == 64 && k_per_wg > 1024) {          // (the dispatcher sends reductions past the cap here only: gemm_plan.h ad_narrow)
         if (b_kmajor) hipLaunchKernelGGL((gemm_ad_kernel<64, 2, 3, true, 0, 64, true>), grid, block, 0, st, a);
         else          hipLaunchKernelGGL((gemm_ad_kernel<64, 2, 3, false, 0, 64, true>), grid, block, 0, st, a);
     } else

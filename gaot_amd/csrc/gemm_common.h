@@ -312,9 +312,9 @@ __device__ __forceinline__ void epilogue_swiglu(const GemmArgs& p, float* smem, 
     if (p.c_amax != nullptr) amax_publish(p.c_amax, amax, lane, (int)blockIdx.x * 4 + wave);
 }
 
-// skinny VALU paths (skinny.hip); return true if they handled the product
-bool launch_skinny(const GemmArgs& a, bool a_kmajor, bool b_kmajor, hipStream_t st);
-bool skinny_would(const GemmArgs& a, bool a_kmajor, bool b_kmajor);
+// skinny VALU paths (skinny.hip): `kind` is the plan's SkinnyTN / SkinnyK / SkinnyN (gemm_plan.h)
+enum class GemmFamily;
+void launch_skinny(const GemmArgs& a, GemmFamily kind, bool b_kmajor, hipStream_t st);
 // LDS-direct (global_load_lds) tile kernels (gemm_glds.hip); tile: 1 = 128x128 (8 waves), 2 = 128x64, 3 = 64x64
 void launch_glds(GemmArgs& a, bool a_kmajor, bool b_kmajor, int tile, hipStream_t st);
 

@@ -5,7 +5,7 @@
 //                                       thousands of rows) -- a handful of scaled column sums
 // All three keep the GEMM descriptor semantics (same epilogue) so callers never see the difference.
 #include "gemm_common.h"
-
+#include "gemm_plan.h"
 namespace gaot {
 
 // ---- A: thread per output element, lanes along n (coalesced stores; A row is a broadcast load)
@@ -162,18 +162,9 @@ __global__ __launch_bounds__(256) void skinny_tn_final_kernel(const GemmArgs p, 
     }
 }
 
-// the same decision without a launch (gaot_gemm_path)
-bool skinny_would(const GemmArgs& a, bool ak, bool bk) {
-    if (a.A2 != nullptr) return false;
-    if (!ak && !bk && a.split_k > 1 && a.ws != nullptr && (a.N <= 16 || a.M <= 16) && (long)a.M * a.N <= 4096 && a.K >= 1024) return true;
-    if (!ak || a.split_k > 1 || a.colsum != nullptr) return false;
-    return a.K <= 16 || a.N <= 4;
-}
-
-bool launch_skinny(const GemmArgs& a, bool ak, bool bk, hipStream_t st) {
-    if (a.A2 != nullptr) return false;
-    // C: transposed-A weight gradient with a tiny side and a long reduction (needs the split-K workspace)
-    if (!ak && !bk && a.split_k > 1 && a.ws != nullptr && (a.N <= 16 || a.M <= 16) && (long)a.M * a.N <= 4096 && a.K >= 1024) {
+// which products come here is plan_gemm's decision (gemm_plan.h)
+void launch_skinny(const GemmArgs& a, GemmFamily kind, bool bk, hipStream_t st) {
+    if (kind == GemmFamily::SkinnyTN) {                // transposed-A weight gradient with a tiny side and a long reduction
         const int chunks = a.split_k;
         // narrow side up to 8 (2-D geometry statistics: 7 columns) or up to 16 (3-D: 9 columns, 3-channel inputs of wide layers)
         if (a.N <= 8)       hipLaunchKernelGGL((skinny_tn_partial_kernel<true, 8>), dim3(cdiv(a.M, 64), chunks), dim3(256), 0, st, a, chunks);
@@ -181,25 +172,18 @@ bool launch_skinny(const GemmArgs& a, bool ak, bool bk, hipStream_t st) {
         else if (a.N <= 16) hipLaunchKernelGGL((skinny_tn_partial_kernel<true, 16>), dim3(cdiv(a.M, 64), chunks), dim3(256), 0, st, a, chunks);
         else                hipLaunchKernelGGL((skinny_tn_partial_kernel<false, 16>), dim3(cdiv(a.N, 64), chunks), dim3(256), 0, st, a, chunks);
         hipLaunchKernelGGL(skinny_tn_final_kernel, dim3(cdiv((long)a.M * a.N, 64)), dim3(256), 0, st, a, chunks);
-        return true;
-    }
-    if (!ak || a.split_k > 1 || a.colsum != nullptr) return false;
-    if (a.K <= 16) {                                   // A
+    } else if (kind == GemmFamily::SkinnyK) {          // K <= 16
         long nb = ((long)a.M * a.N + 255) / 256;
         if (nb > 16384) nb = 16384;
         if (bk) hipLaunchKernelGGL(skinny_k_kernel<true>, dim3((unsigned)nb), dim3(256), 0, st, a);
         else    hipLaunchKernelGGL(skinny_k_kernel<false>, dim3((unsigned)nb), dim3(256), 0, st, a);
-        return true;
-    }
-    if (a.N <= 4) {                                    // B
+    } else {                                           // SkinnyN: N <= 4
         int lpr = 1;
         while (lpr < 64 && lpr * 4 < a.K) lpr <<= 1;   // ~4 k per lane, at most one wave per row
         const int rpb = 256 / lpr;
         if (bk) hipLaunchKernelGGL(skinny_n_kernel<true>, dim3(cdiv(a.M, rpb)), dim3(256), 0, st, a, lpr);
         else    hipLaunchKernelGGL(skinny_n_kernel<false>, dim3(cdiv(a.M, rpb)), dim3(256), 0, st, a, lpr);
-        return true;
     }
-    return false;
 }
 
 }  // namespace gaot

@@ -460,8 +460,11 @@ def gemm(M: int, N: int, K: int, A, lda, a_kmajor, B, ldb, b_kmajor, out, ldc, *
         path = _gemm_path(d, key)
         if _GEMM_TRACE and key not in _GEMM_TRACE_SEEN:          # tools: every distinct product once, with the tile family the dispatcher answers
             _GEMM_TRACE_SEEN.add(key)
+            pl = (C.c_int32 * 8)()
+            L.check(L.load().gaot_debug_gemm_plan(C.byref(d), pl), "gaot_debug_gemm_plan")
+            fam = ("skinny TN", "skinny K", "skinny N", "register-staged", "LDS-direct", "staged split", "all-DMA")[pl[1]]
             print(f"[gemm] {kind} M={M} N={N} K={K} split_k={split_k} raw={int(raw_slabs)} act={act} planes={int(has_planes)} A2={int(A2 is not None)} -> "
-                  f"{ {1: 'fp32-MFMA tiles', 2: 'skinny', 3: 'fp16-piece tiles'}.get(path, path) }", flush=True)
+                  f"{ {1: 'fp32-MFMA tiles', 2: 'skinny', 3: 'fp16-piece tiles'}.get(path, path) }: {fam} {pl[2]} x {pl[3]}, {pl[5]} K slab(s)", flush=True)
         d.pieces, d.a_absmax, d.b_absmax, d.a2_absmax = 3, None, None, None
         d.b_planes, d.ld_bplanes, d.b_plane_stride = None, 0, 0
         if path == 3:
@@ -535,7 +538,7 @@ def _split_for_reduction(Mo: int, No: int, K: int) -> int:
     t128 = ((Mo + 127) // 128) * ((No + 127) // 128)
     if _GEMM_MODE >= 4 and K % 32 == 0 and Mo % 4 == 0 and No % 4 == 0 and min(Mo, No) >= 128 and t128 >= 8:
         # split-bf16 128x128 tiles (gemm_split.hip): ~512 workgroups, at least 256 reduction rows per slab
-        # ... and at most 1 024 per slab (the split tiles' accumulation cap, gemm.hip)
+        # ... and at most 1 024 per slab (the split tiles' accumulation cap, csrc/gemm_plan.h)
         return int(max(1, min(512 // t128, K // 256), -(-K // 1024)))
     tiles = ((Mo + 63) // 64) * ((No + 63) // 64)
     want = max(1, 1024 // max(1, tiles))          # ~1024 workgroups of 64x64 (tools/gemm_bench.py sweep)
@@ -571,28 +574,28 @@ def _split_for_narrow_output(Mo: int, No: int, K: int, planes=None) -> int:
         return 4 if K >= 2048 else _NARROW_SPLIT_1K
     if _NARROW_TILES_1K and 48 <= t128 < 100 and 128 < No <= 256 and K <= 1024 and Mo % 64 == 0 and (planes is None or planes()):
         # two tiles across, half a round of 64-row tiles (4 096 tokens x 256, the FFN down-projection at K = 1 024): the 64 x 64 all-DMA
-        # tiles (gemm.hip, 256 workgroups) take the whole reduction in one launch; two slabs on the fp32-MFMA tiles + the reduce were
+        # tiles (csrc/gemm_plan.h, 256 workgroups) take the whole reduction in one launch; two slabs on the fp32-MFMA tiles + the reduce were
         # 24.8 + 5.3 us per launch (profiles/r5z_c4_kernel_stats_before.txt, r5z_c4_step_sequence.txt).  `planes`: whether the B operand has
-        # pre-split weight planes -- those tiles need them (gemm.hip `ad_narrow`); without (GAOT_WEIGHT_PLANES=0, an unregistered or misaligned
+        # pre-split weight planes -- those tiles need them (csrc/gemm_plan.h `ad_narrow`); without (GAOT_WEIGHT_PLANES=0, an unregistered or misaligned
         # weight view, B an activation) the product keeps its K slabs below instead of running unsplit on ~128 fp32-MFMA workgroups
         return 1
     if 48 <= t128 < 100 and Mo >= 128 and No >= 128:
         # fewer than 100 output tiles (4 096 tokens x 384 at the 3-D configuration): on the fp32-MFMA tiles 130 us at K = 3 072;
-        # enough K slabs for ~256 workgroups on the split-bf16 tiles, each at most 1 024 deep (the accumulation cap of gemm.hip)
+        # enough K slabs for ~256 workgroups on the split-bf16 tiles, each at most 1 024 deep (the accumulation cap of csrc/gemm_plan.h)
         s = min(-(-256 // t128), K // 512)
         while s > 0 and K / s > 1024 and s < K // 256:
             s += 1
         s = max(1, s)
         # [r6] slabs that would not fill the split tiles either (s x tiles < 250: they ran on the fp32-MFMA tiles -- 4 096 x 384 x 1 152 in two
         # slabs of 39 us + a reduce) with a reduction of at most 2 048: unsplit on the 64 x 64 all-DMA tiles, whose kernel flushes its
-        # accumulators every 1 024 values of k (gemm.hip `long_k`; needs the weight planes like every product on those tiles)
+        # accumulators every 1 024 values of k (csrc/gemm_plan.h `long_k`; needs the weight planes like every product on those tiles)
         if s > 1 and s * t128 < 250 and 1024 < K <= 2048 and K % 32 == 0 and Mo % 64 == 0 and 128 < No <= 384 and planes is not None and planes() \
                 and int(L.load().gaot_debug_set_gemm_ad_flush(-1)) == 1:          # (-1: query)
             return 1
         return s
     if t128 >= 200 and K > 1024 and Mo >= 128 and No >= 128:
         # plenty of tiles, long reduction (C3: 16 384 x 256 x 2 048): the split-bf16 tiles accumulate at most 1 024 values of k per
-        # workgroup (gemm.hip), so the reduction arrives in slabs of that depth rather than falling back to the fp32-MFMA tiles
+        # workgroup (csrc/gemm_plan.h), so the reduction arrives in slabs of that depth rather than falling back to the fp32-MFMA tiles
         # (165 vs 123 us per launch at that shape)
         return -(-K // 1024)
     return 1

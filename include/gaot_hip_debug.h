@@ -20,6 +20,12 @@ int gaot_debug_set_gemm_ablate(int bits);
 /* which kernel family served the calling thread's last gaot_gemm_f32: 1 = fp32 MFMA tiles, 2 = skinny VALU path,
  * 3 = split-bf16 MFMA tiles (fp32 operands split exactly into three bf16 pieces, six bf16 MFMAs per product, fp32-level error) */
 int gaot_debug_last_gemm_path(void);
+/* which kernel gaot_gemm_f32 WOULD run this product on, under the switches as they stand (csrc/gemm_plan.h; launches nothing and reads
+ * no memory through the descriptor's pointers): out = {path (as gaot_gemm_path), family (0 / 1 / 2 skinny TN / K / N kernels, 3 register-
+ * staged fp32 tiles, 4 LDS-direct fp32 tiles, 5 staged split tiles, 6 all-DMA fp16-piece tiles), tile rows, tile columns, variant (family 3:
+ * the configuration as gaot_debug_set_gemm_tile numbers them, 4: tile id 1 .. 3, 5: tile height), K slabs, the reduce that follows (0 none,
+ * 1 vector, 2 scalar), whether an absmax launch over C follows when c_absmax is given}; GAOT_OK, or the descriptor's error */
+int gaot_debug_gemm_plan(const gaot_gemm_desc* d, int32_t out[8]);
 /* tuning hook: 0 = register-staged fp32 tiles only, 1 = + LDS-direct fp32 tiles (2-stage ring), 3 = same with a 3-stage
  * ring, 4 = + split-bf16 tiles where the heuristic picks them (DEFAULT), 5 = split-bf16 wherever eligible, 6 = split-bf16
  * for the SwiGLU-gate product only */
@@ -36,7 +42,7 @@ int gaot_debug_set_gemm_ad(int on);
  * A/B; bit-identical results); returns the old value */
 int gaot_debug_set_gemm_aux_prefetch(int on);
 /* 64 x 64 all-DMA tiles for narrow outputs (N <= 256), bits: 1 (default) launches that 64 x 128 tiles leave half filled (4 096-token
- * batches), 2 also K <= 256 at full launches (off: slower at step level); 0 none (same-box A/B; see the dispatcher in gemm.hip);
+ * batches), 2 also K <= 256 at full launches (off: slower at step level); 0 none (same-box A/B; see csrc/gemm_plan.h);
  * returns the old value */
 int gaot_debug_set_gemm_ad_narrow(int on);
 /* attention backward, head_dim 32, fp16 pieces: 1 (default) lets two workgroups share the query tiles of a 256-key block when the launch
