@@ -228,6 +228,11 @@ PROTOTYPES = {
                                          _f, _f, _f, _f, _f, _f, C.c_int32, C.c_int32, _i, C.c_int32, _f, _f, _f, _i, _s]),
     "gaot_seq_test_compose": (C.c_int, [_f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _f, _f, _f, _i, C.c_int32, _i,
                                         C.c_int32, _f, _f, _i, _s]),
+    "gaot_graph_store_scratch": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float]),
+    "gaot_rescale_batch": (C.c_int, [_f, C.c_int32, C.c_int32, C.c_int32, _f, _s]),
+    "gaot_graph_store_count": (C.c_int, [_f, C.c_int32, C.c_int32, _f, C.c_int32, C.c_int32, C.c_float, _i, _i, _i, _i, _i, C.c_void_p, _s]),
+    "gaot_graph_store_fill": (C.c_int, [_f, C.c_int32, C.c_int32, _f, C.c_int32, C.c_int32, C.c_float, _i, C.c_int64, C.c_int32, C.c_int32, _i, _i,
+                                        _i, _i, _i, _i, _i, _i, _i, _i, C.c_void_p, _i, _s]),
 }
 
 _lib = None

@@ -95,6 +95,23 @@ class GeometryPlan:
         self._groups: Dict[tuple, dict] = {}          # per coordinate pair (by shapes): kept bytes + the arrays derived from them
         self.epoch = 0                # bumped whenever a coordinate-derived array may have been refreshed in place
 
+    @classmethod
+    def from_arrays(cls, Q: int, E: int, n_src: int, index, splits, edge_query, t_splits, t_edge, deg, max_deg, max_t_deg, index_long=None,
+                    src_index=None) -> "GeometryPlan":
+        """A full plan over READY device arrays, laid out as gaot_csr_prepare / gaot_csr_transpose leave them (int32; index / edge_query /
+        t_edge of max(E, 1) entries, splits [Q + 1], t_splits [n_src + 1], edge ids ascending inside a source) with `deg` the int64 row
+        lengths and the two maximum degrees known on the host: nothing is launched, nothing is validated -- for lists that are valid by
+        construction (graphs.GraphStore).  `src_index`: the neighbour dict's own index tensor, for plan_for / has_plan to recognise."""
+        p = cls(None, None, 0)
+        p.Q, p.E, p.n_src = int(Q), int(E), int(n_src)
+        p.index, p.splits, p.edge_query, p.t_splits, p.t_edge, p.deg = index, splits, edge_query, t_splits, t_edge, deg
+        p.max_deg, p.max_t_deg = (0, 0) if p.E == 0 else (int(max_deg), int(max_t_deg))
+        p._inv_deg_edge = p._edge_query_long = None
+        p._index_long = index_long
+        p._coord_cache, p._groups, p.epoch = {}, {}, 0
+        p._src_id = None if src_index is None else (id(src_index), src_index._version)
+        return p
+
     SKEW_DEGREE = 48      # rows longer than this (or unknown) go to the edge-partitioned kernels
 
     def part_pointers(self):

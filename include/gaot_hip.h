@@ -706,6 +706,43 @@ int gaot_seq_test_compose(const float* u, const float* c, int32_t S, int32_t T, 
                           const float* u_std, const float* c_mean, const float* c_std, const int32_t* idx, int32_t B, const int32_t* tidx,
                           int32_t K, float* x0, float* yseq, int32_t* status_flag, gaot_stream_t stream);
 
+/* ---- dataset-level graph building for variable-coordinate (vx) runs (csrc/graph_store.hip) ------------------------------------------
+ * The reference's GraphBuilder.build_graphs_for_split (src/datasets/graph_builder.py:28-87; called by build_all_graphs :89-144 from
+ * both trainers) loops over the samples of a split in Python: rescale(x, (-1, 1)) (src/utils/scaling.py:10-35), then for every scale
+ * one radius search physical -> latent (:62-69) and one latent -> physical (:71-78).  These entry points do that for all S samples in a
+ * number of launches that does not depend on S (rescale 1, count 7, fill 7).
+ *
+ * gaot_rescale_batch: out[s] = ((x[s] - min) / range) * 2 + (-1) per sample and dimension, min / max over the sample's N points, a
+ *   range of 0 replaced by 1; each operation rounded on its own: the torch expression bit for bit.  x, out: fp32 [S, N, dim], dim 1..3.
+ *
+ * gaot_graph_store_count (per scale): xs [S, N, dim] are the RESCALED coordinates (inside [-1, 1]^dim), latent [Q, dim] the shared
+ *   tokens, dim 2 or 3.  Writes per-sample row splits of both directions, each sample's starting at 0 -- enc_splits int64 [S, Q + 1]
+ *   (rows = tokens, entries = physical points), dec_splits int64 [S, N + 1] (rows = physical points, entries = tokens), their int32
+ *   copies -- and stats int64 [S, 3] = (edge count, longest encoder row, longest decoder row) per sample: what the caller reads back to
+ *   size the arenas.  The test is radius.hip's inclusive `dist <= radius`, exactly symmetric, so both directions hold the same pairs.
+ *   scratch: gaot_graph_store_scratch(...) bytes, 8-byte aligned, any content; it carries the cell list to gaot_graph_store_fill.
+ *
+ * gaot_graph_store_fill (per scale, after the count on the same scratch and unchanged xs): offsets int64 [S + 1] on the device are the
+ *   exclusive sums of the samples' edge counts (offsets[S] = total), max_edges the largest sample's count (each below 2^31: the caller
+ *   refuses larger ones), max_row the longest row of either direction.  Sample s owns entries offsets[s] .. offsets[s + 1] of every
+ *   arena (all of `total` entries):
+ *     enc_index / dec_index int64          the reference-style neighbors_index lists, every row in ascending index
+ *     *_index32, *_edge_query int32        as gaot_csr_prepare leaves them
+ *     *_t_edge int32                       as gaot_csr_transpose leaves it (edge ids ascending inside a source); the matching t_splits
+ *                                          of one direction are the splits32 of the other
+ *   sort_scratch: int64 [total], needed when max_row > 4096 (may be NULL otherwise).  No output depends on the order in which atomics
+ *   arrive: two builds give equal bytes. */
+int64_t gaot_graph_store_scratch(int32_t S, int32_t N, int32_t Q, int32_t dim, float radius);
+int gaot_rescale_batch(const float* x, int32_t S, int32_t N, int32_t dim, float* out, gaot_stream_t stream);
+int gaot_graph_store_count(const float* xs, int32_t S, int32_t N, const float* latent, int32_t Q, int32_t dim, float radius,
+                           int64_t* enc_splits, int64_t* dec_splits, int32_t* enc_splits32, int32_t* dec_splits32, int64_t* stats,
+                           void* scratch, gaot_stream_t stream);
+int gaot_graph_store_fill(const float* xs, int32_t S, int32_t N, const float* latent, int32_t Q, int32_t dim, float radius,
+                          const int64_t* offsets, int64_t total, int32_t max_edges, int32_t max_row, const int32_t* enc_splits32,
+                          const int32_t* dec_splits32, int64_t* enc_index, int64_t* dec_index, int32_t* enc_index32,
+                          int32_t* dec_index32, int32_t* enc_edge_query, int32_t* dec_edge_query, int32_t* enc_t_edge,
+                          int32_t* dec_t_edge, void* scratch, int64_t* sort_scratch, gaot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
