@@ -233,6 +233,9 @@ PROTOTYPES = {
     "gaot_graph_store_count": (C.c_int, [_f, C.c_int32, C.c_int32, _f, C.c_int32, C.c_int32, C.c_float, _i, _i, _i, _i, _i, C.c_void_p, _s]),
     "gaot_graph_store_fill": (C.c_int, [_f, C.c_int32, C.c_int32, _f, C.c_int32, C.c_int32, C.c_float, _i, C.c_int64, C.c_int32, C.c_int32, _i, _i,
                                         _i, _i, _i, _i, _i, _i, _i, _i, C.c_void_p, _i, _s]),
+    "gaot_union_compose_indexed": (C.c_int, [C.c_void_p, C.c_int32, _i, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             _i, _i, _i, _i, _i, _f, _f, _i, _i, _s]),
+    "gaot_sample_gather": (C.c_int, [_f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i, C.c_int32, _f, _f, _f, _i, _s]),
 }
 
 _lib = None

@@ -10,7 +10,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libgaot_hip.so")
 SOURCES = ["capi.cpp", "gemm.hip", "gemm_glds.hip", "gemm_split.hip", "gemm_ad.hip", "skinny.hip", "gno.hip", "gno_ep.hip", "edge_drop.hip", "kernel_mlp.hip", "radius.hip", "pointwise.hip", "glue.hip", "attention.hip", "attention_wide.hip", "metrics.hip"]
 # translation units added since: kept in a list of their own because tests/test_eval_metrics_cpu.py pins len(SOURCES) at the sixteen above
-DATA_SOURCES = ["seq_pairs.hip", "graph_store.hip"]
+DATA_SOURCES = ["seq_pairs.hip", "graph_store.hip", "sample_store.hip"]
 ALL_SOURCES = SOURCES + DATA_SOURCES
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "segsort.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_plan.h"), os.path.join(CSRC, "attention_common.h"), os.path.join(HERE, "..", "include", "gaot_hip.h"), os.path.join(HERE, "..", "include", "gaot_hip_debug.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-array-bounds"] + os.environ.get("GAOT_HIPCC_EXTRA", "").split()      # (extra: A/B builds, tools)

@@ -93,6 +93,41 @@ __global__ void concat_offset_kernel(ConcatParts p, int total, int* __restrict__
 // every step, the launch does not).  All arrays are static buffers sized for E_cap >= sum of the parts' edge counts; the edges past the
 // real count ("pads") are never referenced by a row of either CSR (splits[Q] = t_splits[n_src] = E_real), and the flat per-edge kernels
 // that do walk them see valid indices (source 0, query 0, t_edge = own id) and an edge scale of 0.
+// The body both compose kernels share.  `begin` [B + 1] (LDS): the position of every batch entry's first edge in the union and, last, the
+// union's edge count, none above E_cap; batch entry b is table row sel[b] (INDEXED, LDS) or row b.  Offsets are added without sign (two
+// values below 2^31 each) and cut at the real count, a transposed edge id also at the capacity: with a union that fits -- the only kind
+// the host-fed kernel is ever handed -- neither cut changes a value, and in a truncated one every stored entry still names a slot of the
+// arrays it indexes.
+template <bool INDEXED>
+__device__ __forceinline__ void union_compose_body(const gaot_union_part* __restrict__ parts, const int* __restrict__ sel,
+                                                   const int* __restrict__ begin, int B, int Qe, int Se, int dsrc, int ddst, int E_cap,
+                                                   int* __restrict__ index, int* __restrict__ eq, int* __restrict__ tedge,
+                                                   int* __restrict__ splits, int* __restrict__ tsplits, float* __restrict__ src,
+                                                   float* __restrict__ dst, int* __restrict__ e_real) {
+#define UNION_PART(b) parts[INDEXED ? sel[(b)] : (b)]
+    const int E = min(begin[B], E_cap);
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *e_real = E;
+    if (i < E_cap) {
+        if (i < E) {
+            int lo = 0, hi = B;                       // begin[lo] <= i < begin[hi]
+            while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (begin[mid] <= (int)i) lo = mid; else hi = mid; }
+            const gaot_union_part& p = UNION_PART(lo);
+            const int l = (int)i - begin[lo];
+            index[i] = p.index[l] + lo * Se;
+            eq[i] = p.edge_query[l] + lo * Qe;
+            tedge[i] = (int)min((unsigned)p.t_edge[l] + (unsigned)begin[lo], (unsigned)E_cap - 1u);
+        } else {
+            index[i] = 0; eq[i] = 0; tedge[i] = (int)i;
+        }
+    }
+    const long Qt = (long)B * Qe, St = (long)B * Se;
+    if (i <= Qt) splits[i] = i == Qt ? E : (int)min((unsigned)UNION_PART(i / Qe).splits[i % Qe] + (unsigned)begin[i / Qe], (unsigned)E);
+    if (i <= St) tsplits[i] = i == St ? E : (int)min((unsigned)UNION_PART(i / Se).t_splits[i % Se] + (unsigned)begin[i / Se], (unsigned)E);
+    if (src && i < St * dsrc) { const long r = i / dsrc; src[i] = UNION_PART(r / Se).src[(r % Se) * dsrc + i % dsrc]; }
+    if (dst && i < Qt * ddst) { const long r = i / ddst; dst[i] = UNION_PART(r / Qe).dst[(r % Qe) * ddst + i % ddst]; }
+#undef UNION_PART
+}
 __global__ __launch_bounds__(256) void union_compose_kernel(const gaot_union_part* __restrict__ parts, int B, int Qe, int Se, int dsrc, int ddst,
                                                             int E_cap, int* __restrict__ index, int* __restrict__ eq, int* __restrict__ tedge,
                                                             int* __restrict__ splits, int* __restrict__ tsplits, float* __restrict__ src,
@@ -101,27 +136,76 @@ __global__ __launch_bounds__(256) void union_compose_kernel(const gaot_union_par
     for (int b = threadIdx.x; b < B; b += 256) begin[b] = parts[b].e_begin;
     if (threadIdx.x == 0) begin[B] = parts[B - 1].e_begin + parts[B - 1].e_count;
     __syncthreads();
-    const int E = min(begin[B], E_cap);
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i == 0) *e_real = E;
-    if (i < E_cap) {
-        if (i < E) {
-            int lo = 0, hi = B;                       // begin[lo] <= i < begin[hi]
-            while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (begin[mid] <= (int)i) lo = mid; else hi = mid; }
-            const gaot_union_part& p = parts[lo];
-            const int l = (int)i - begin[lo];
-            index[i] = p.index[l] + lo * Se;
-            eq[i] = p.edge_query[l] + lo * Qe;
-            tedge[i] = p.t_edge[l] + begin[lo];
-        } else {
-            index[i] = 0; eq[i] = 0; tedge[i] = (int)i;
-        }
+    union_compose_body<false>(parts, nullptr, begin, B, Qe, Se, dsrc, ddst, E_cap, index, eq, tedge, splits, tsplits, src, dst, e_real);
+}
+// The same union for a DEVICE list of B rows of a table that describes a whole dataset (graphs.GraphStore.part_table): batch entry b is
+// all_parts[idx[b]], and where its edges begin is not in the table -- it depends on the rest of the batch.  Every workgroup takes the
+// exclusive prefix sum of the B indexed edge counts itself: four consecutive entries per thread, a shuffle scan over the 64 running sums of
+// a wave, the four wave totals through LDS.  The sums saturate at E_cap + 1 (64-bit adds of values that are each at most 2^31), so a batch
+// that does not fit -- only a list with repeated samples can exceed a capacity sized for the B largest -- is known exactly, flagged (|= 4) and
+// truncated at the capacity; an index outside [0, S) is clamped and flagged (|= 1).  The first workgroup reports.
+__global__ __launch_bounds__(256) void union_compose_indexed_kernel(const gaot_union_part* __restrict__ parts, int S,
+                                                                    const int* __restrict__ idx, int B, int Qe, int Se, int dsrc, int ddst,
+                                                                    int E_cap, int* __restrict__ index, int* __restrict__ eq,
+                                                                    int* __restrict__ tedge, int* __restrict__ splits, int* __restrict__ tsplits,
+                                                                    float* __restrict__ src, float* __restrict__ dst, int* __restrict__ e_real,
+                                                                    int* __restrict__ flag) {
+    __shared__ int begin[1025];
+    __shared__ int sel[1024];
+    __shared__ unsigned wave_sum[4];
+    const int t = threadIdx.x;
+    int bad = 0;
+    for (int b = t; b < B; b += 256) {
+        const int v = idx[b];
+        if (v < 0 || v >= S) bad = 1;
+        sel[b] = v < 0 ? 0 : (v >= S ? S - 1 : v);
     }
-    const long Qt = (long)B * Qe, St = (long)B * Se;
-    if (i <= Qt) splits[i] = i == Qt ? E : min(parts[i / Qe].splits[i % Qe] + begin[i / Qe], E);
-    if (i <= St) tsplits[i] = i == St ? E : min(parts[i / Se].t_splits[i % Se] + begin[i / Se], E);
-    if (src && i < St * dsrc) { const long r = i / dsrc; src[i] = parts[r / Se].src[(r % Se) * dsrc + i % dsrc]; }
-    if (dst && i < Qt * ddst) { const long r = i / ddst; dst[i] = parts[r / Qe].dst[(r % Qe) * ddst + i % ddst]; }
+    __syncthreads();
+    const unsigned long long cap = (unsigned long long)E_cap + 1ull;
+    unsigned cnt[4], own = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int b = 4 * t + k;
+        cnt[k] = b < B ? (unsigned)min((unsigned long long)max(parts[sel[b]].e_count, 0), cap) : 0u;
+        own = (unsigned)min((unsigned long long)own + cnt[k], cap);
+    }
+    const int lane = t & 63, wave = t >> 6;
+    unsigned incl = own;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned up = __shfl_up(incl, off, 64);
+        if (lane >= off) incl = (unsigned)min((unsigned long long)up + incl, cap);
+    }
+    if (lane == 63) wave_sum[wave] = incl;
+    const unsigned before = __shfl_up(incl, 1, 64);
+    __syncthreads();
+    unsigned long long run = lane > 0 ? before : 0u;
+    for (int w = 0; w < wave; ++w) run += wave_sum[w];
+    run = min(run, cap);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int b = 4 * t + k;
+        if (b <= B) begin[b] = (int)min(run, (unsigned long long)E_cap);
+        run = min(run + cnt[k], cap);
+    }
+    if (4 * t + 4 == B) begin[B] = (int)min(run, (unsigned long long)E_cap);
+    // (thread (B - 1) / 4 holds the batch's whole count in `run`: every entry after B - 1 added 0)
+    if (blockIdx.x == 0) {
+        const int flags = bad | ((t == (B - 1) / 4 && run > (unsigned long long)E_cap) ? 4 : 0);
+        if (flags) atomicOr(flag, flags);
+    }
+    __syncthreads();
+    union_compose_body<true>(parts, sel, begin, B, Qe, Se, dsrc, ddst, E_cap, index, eq, tedge, splits, tsplits, src, dst, e_real);
+}
+// threads of a compose launch: one per entry of the longest array it writes
+static inline long union_compose_threads(long B, long Qe, long Se, long dsrc, long ddst, long E_cap, bool src, bool dst) {
+    long n = E_cap;
+    const long Qt = B * Qe, St = B * Se;
+    if (Qt + 1 > n) n = Qt + 1;
+    if (St + 1 > n) n = St + 1;
+    if (src && St * dsrc > n) n = St * dsrc;
+    if (dst && Qt * ddst > n) n = Qt * ddst;
+    return n;
 }
 // 1 / deg(query(e)) per edge, 0 on the pads ('mean' reduction of agno.py:264 as a per-edge scale)
 __global__ void edge_inv_degree_kernel(const int* __restrict__ sp, const int* __restrict__ eq, int E, const int* __restrict__ e_real,
@@ -714,15 +798,25 @@ extern "C" int gaot_union_compose(const gaot_union_part* parts_dev, int32_t n_pa
     GAOT_REQUIRE(parts_dev && n_parts >= 1 && n_parts <= 1024 && q_each > 0 && n_src_each > 0 && e_cap >= 1 && dim_src >= 0 && dim_dst >= 0,
                  "union_compose: bad sizes (1 <= n_parts <= 1024, q_each, n_src_each, e_cap > 0)");
     GAOT_REQUIRE(index32 && edge_query && t_edge && splits32 && t_splits && e_real, "union_compose: null output pointer");
-    long n = e_cap;
-    const long Qt = (long)n_parts * q_each, St = (long)n_parts * n_src_each;
-    if (Qt + 1 > n) n = Qt + 1;
-    if (St + 1 > n) n = St + 1;
-    if (src && St * dim_src > n) n = St * dim_src;
-    if (dst && Qt * dim_dst > n) n = Qt * dim_dst;
+    const long n = union_compose_threads(n_parts, q_each, n_src_each, dim_src, dim_dst, e_cap, src != nullptr, dst != nullptr);
     hipLaunchKernelGGL(union_compose_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ST(stream), parts_dev, n_parts, q_each, n_src_each, dim_src,
                        dim_dst, e_cap, index32, edge_query, t_edge, splits32, t_splits, src, dst, e_real);
     GAOT_CHECK_LAUNCH("gaot_union_compose");
+    return GAOT_OK;
+}
+
+extern "C" int gaot_union_compose_indexed(const gaot_union_part* all_parts_dev, int32_t S, const int32_t* idx_dev, int32_t n_parts, int32_t q_each,
+                                          int32_t n_src_each, int32_t dim_src, int32_t dim_dst, int32_t e_cap, int32_t* index32,
+                                          int32_t* edge_query, int32_t* t_edge, int32_t* splits32, int32_t* t_splits, float* src, float* dst,
+                                          int32_t* e_real, int32_t* status_flag, gaot_stream_t stream) {
+    GAOT_REQUIRE(all_parts_dev && S >= 1 && idx_dev && n_parts >= 1 && n_parts <= 1024 && q_each > 0 && n_src_each > 0 && e_cap >= 1 && dim_src >= 0 &&
+                     dim_dst >= 0,
+                 "union_compose_indexed: null table / index list or bad sizes (S >= 1, 1 <= n_parts <= 1024, q_each, n_src_each, e_cap > 0)");
+    GAOT_REQUIRE(index32 && edge_query && t_edge && splits32 && t_splits && e_real && status_flag, "union_compose_indexed: null output pointer");
+    const long n = union_compose_threads(n_parts, q_each, n_src_each, dim_src, dim_dst, e_cap, src != nullptr, dst != nullptr);
+    hipLaunchKernelGGL(union_compose_indexed_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ST(stream), all_parts_dev, S, idx_dev, n_parts, q_each,
+                       n_src_each, dim_src, dim_dst, e_cap, index32, edge_query, t_edge, splits32, t_splits, src, dst, e_real, status_flag);
+    GAOT_CHECK_LAUNCH("gaot_union_compose_indexed");
     return GAOT_OK;
 }
 

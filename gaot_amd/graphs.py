@@ -107,6 +107,7 @@ class GraphStore:
         dev = x.device
         x = x.contiguous().float()
         latent = latent.contiguous().float()
+        self.latent = latent                           # the shared token coordinates: what part_table()'s stride-0 column points at
         i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
         self.x_scaled = _alloc(S, N, dim, dtype=torch.float32, device=dev)
         L.check(lib.gaot_rescale_batch(_p(x), S, N, dim, _p(self.x_scaled), _stream()), "gaot_rescale_batch")
@@ -169,6 +170,62 @@ class GraphStore:
     def arenas(self, scale: int) -> dict:
         """the allocations behind scale `scale` of a device store (name -> tensor; per-sample entries offsets[s] .. offsets[s + 1])"""
         return self._arenas[scale]
+
+    # ---- index-driven batches (plan.StaticUnion.bind_index, trainer.bind_samples): the whole split as ONE table per scale and side
+    def part_table(self, scale: int, side: str) -> torch.Tensor:
+        """device int64 [S, 8]: one gaot_union_part per sample -- the addresses of its plan arrays inside the arenas, its coordinates
+        (`side` 'encoder': x_scaled[s] as sources, the shared latent grid with stride 0 as queries; 'decoder': the reverse) and its edge
+        count in the high half of the last word (the low half, e_begin, depends on the batch: the indexed compose kernel takes the prefix
+        sum itself).  Built once, vectorised on the host, one upload; the store must outlive whoever reads it.  Device stores only."""
+        if side not in ("encoder", "decoder"):
+            raise ValueError(f"GraphStore.part_table: side must be 'encoder' or 'decoder', got {side!r}")
+        if not self._arenas:
+            raise RuntimeError("GraphStore.part_table: a store built from host tensors has no device arenas to point into (build it from "
+                               "device tensors; there is no fallback)")
+        key = (int(scale), side)
+        hit = self.__dict__.setdefault("_part_tables", {}).get(key)
+        if hit is not None:
+            return hit
+        a = self._arenas[scale]
+        S, N, Q = self.S, self.N, self.Q
+        counts = self.edge_counts[:, scale].numpy().astype(np.int64)
+        offs = np.concatenate(([0], np.cumsum(counts)[:-1])).astype(np.int64)
+        s = np.arange(S, dtype=np.int64)
+        pre, other, rows, t_rows = ("enc", "dec", Q, N) if side == "encoder" else ("dec", "enc", N, Q)
+        tab = np.zeros((S, 8), dtype=np.int64)
+        for col, name in enumerate((f"{pre}_index32", f"{pre}_edge_query", f"{pre}_t_edge")):
+            tab[:, col] = a[name].data_ptr() + 4 * offs
+        tab[:, 3] = a[f"{pre}_splits32"].data_ptr() + 4 * (rows + 1) * s
+        tab[:, 4] = a[f"{other}_splits32"].data_ptr() + 4 * (t_rows + 1) * s
+        x_ptr = self.x_scaled.data_ptr() + 4 * N * self.dim * s
+        lat_ptr = np.full(S, self.latent.data_ptr(), dtype=np.int64)
+        tab[:, 5], tab[:, 6] = (x_ptr, lat_ptr) if side == "encoder" else (lat_ptr, x_ptr)
+        tab[:, 7] = counts << 32
+        out = self._part_tables[key] = torch.from_numpy(tab).to(self.x_scaled.device)
+        return out
+
+    def batch_edge_capacity(self, B: int, scale: int) -> int:
+        """edge capacity of the ONE static union that serves every batch of B samples of this split at `scale` (batch_edge_capacity below)"""
+        return batch_edge_capacity(self.edge_counts[:, scale], B)
+
+
+def batch_edge_capacity(counts, B: int) -> int:
+    """plan.edge_bucket(sum of the B largest per-sample edge counts): any batch of B DISTINCT samples fits a union of this capacity, so one
+    capacity -- one captured step -- serves the whole split whatever the shuffle.  B > S has no batch of distinct samples: an epoch's order
+    then repeats the list (trainer.shard_indices), every sample at most ceil(B / S) times, and that is what is summed (the counts in
+    descending order, cycled to B entries).  A list that repeats samples beyond that can exceed the capacity: the compose kernel flags it
+    (status & 4) and truncates.  Capacities from 2^31 on are refused: the unions' edge ids are int32."""
+    from .plan import edge_bucket
+    c = np.sort(np.asarray(counts, dtype=np.int64).reshape(-1))[::-1]
+    B = int(B)
+    if B < 1 or c.size == 0:
+        raise ValueError("batch_edge_capacity: needs at least one sample and a batch of at least one")
+    total = int(c[np.arange(B) % c.size].sum())
+    cap = edge_bucket(total)
+    if cap >= (1 << 31):
+        raise ValueError(f"batch_edge_capacity: a batch of {B} samples can hold {total} edges; a union's edge list must stay below 2^31 entries "
+                         "(smaller batches, or a smaller radius)")
+    return cap
 
 
 class GraphBuilder:

@@ -176,6 +176,30 @@ class _MAGNOBase(nn.Module):
             out.append(su)
         return out
 
+    _graph_side = None       # 'encoder' / 'decoder': which of a GraphStore's part tables describes this module's graphs
+
+    def vx_unions_indexed(self, store, idx: torch.Tensor, B: int):
+        """index-driven vx batches (trainer.bind_samples): one static union per scale at the store's batch capacity
+        (graphs.GraphStore.batch_edge_capacity), bound to the store's part table and to the STATIC device index list `idx` [B] -- its
+        refresh() composes whatever samples `idx` names at that moment, so nothing is loaded per step and no bucket is picked: one union,
+        one captured step, for every batch of the split.  The unions are the caller's: they live as long as the step that captured them
+        (they are not entered into the module's cache of host-fed unions, whose eviction would not know about the capture)."""
+        if not (_plan.VX_STATIC and bool(self.precompute_edges) and not self.node_embedding):
+            raise RuntimeError("vx_unions_indexed: index-driven vx batches need static unions (GAOT_VX_STATIC), precompute_edges=True and no "
+                               "node_embedding")
+        if len(store.radii) != len(self.scales):
+            raise ValueError(f"vx_unions_indexed: the store holds {len(store.radii)} scales, the module has {len(self.scales)}")
+        if store.dim != self.coord_dim:
+            raise ValueError(f"vx_unions_indexed: the store's coordinates have {store.dim} dimensions, the module expects {self.coord_dim}")
+        n_src, n_dst = (store.N, store.Q) if self._graph_side == "encoder" else (store.Q, store.N)
+        out = []
+        for si in range(len(self.scales)):
+            table = store.part_table(si, self._graph_side)          # (raises for a host store)
+            su = _plan.StaticUnion(B, n_src, n_dst, store.dim, store.dim, store.batch_edge_capacity(B, si), table.device)
+            su.bind_index(table, store.S, idx, hold=store)
+            out.append(su)
+        return out
+
     def _kcoord(self, c: torch.Tensor) -> torch.Tensor:
         """kernel coordinates: raw or node_pos_encode()d (cached per tensor identity: geometry only)."""
         if not self.node_embedding:
@@ -321,6 +345,7 @@ class _MAGNOBase(nn.Module):
 
 class MAGNOEncoder(_MAGNOBase):
     """physical nodes -> latent tokens."""
+    _graph_side = "encoder"
 
     def __init__(self, in_channels: int, out_channels: int, config: MAGNOConfig):
         super().__init__()
@@ -371,6 +396,7 @@ class MAGNOEncoder(_MAGNOBase):
 
 class MAGNODecoder(_MAGNOBase):
     """latent tokens -> query nodes, then the output projection."""
+    _graph_side = "decoder"
 
     def __init__(self, in_channels: int, out_channels: int, config: MAGNOConfig):
         super().__init__()

@@ -709,6 +709,7 @@ class StaticUnion:
         self._hold = (list(plans), src_parent, dst_parent)          # the arrays behind the table's pointers live until the next load
         self.e_real = total
         self.raw = False
+        self._index = None
 
     CHECK_EVERY = 64      # raw lists: the device-side validity flag is read back (one host synchronisation) every so many loads
 
@@ -756,6 +757,7 @@ class StaticUnion:
         self._hold = (list(dicts), src_parent, dst_parent, idx, sps)
         self.e_real = total
         self.raw = True
+        self._index = None
 
     def _transpose(self):
         pl = self.plan
@@ -776,12 +778,37 @@ class StaticUnion:
         else:
             self.load(plans, src_parent, dst_parent)
 
+    def bind_index(self, all_parts: torch.Tensor, S: int, idx: torch.Tensor, hold=None) -> None:
+        """indexed mode: from now on refresh() composes the samples all_parts[idx[b]] -- `all_parts` a device int64 [S, 8] table of
+        gaot_union_part entries for a whole dataset (graphs.GraphStore.part_table), `idx` a STATIC device int32 list of B sample indices whose
+        content the caller rewrites between steps.  No load*() is needed (or allowed to matter) afterwards: the lookup, the positions of the
+        samples' edges and the capacity check happen in the kernel, which ORs into `self.flag` (1: an index outside [0, S) was clamped, 4:
+        the batch's edges exceed the capacity and the union was truncated).  `hold`: whatever owns the arrays the table points into."""
+        dev = self.src.device
+        if all_parts.device != dev or all_parts.dtype != torch.int64 or tuple(all_parts.shape) != (int(S), 8) or not all_parts.is_contiguous():
+            raise ValueError(f"StaticUnion.bind_index: the table must be a contiguous int64 [{int(S)}, 8] tensor on {dev}")
+        if idx.device != dev or idx.dtype != torch.int32 or tuple(idx.shape) != (self.B,) or not idx.is_contiguous():
+            raise ValueError(f"StaticUnion.bind_index: the index list must be a contiguous int32 [{self.B}] tensor on {dev}")
+        self._index = (all_parts, int(S), idx)
+        self._hold = (all_parts, idx, hold)
+        self.raw = False
+        self.e_real = None            # known on the device only (plan.e_dev)
+
+    _index = None         # indexed mode: (table [S, 8], S, static index list [B])
+
     def refresh(self) -> None:
         """compose the union from the loaded table (capturable: a fixed launch over fixed addresses); the derived arrays follow on request"""
         if self._hold is None:
-            raise RuntimeError("gaot_amd: StaticUnion.refresh() before any load(): the device table holds no sample pointers yet")
+            raise RuntimeError("gaot_amd: StaticUnion.refresh() before any load() or bind_index(): the device table holds no sample pointers yet")
         pl = self.plan
-        if self.raw:
+        if self._index is not None:
+            tab, S, idx = self._index
+            pl._tcsr = None
+            L.check(L.load().gaot_union_compose_indexed(_p(tab), S, _p(idx), self.B, self.n_dst, self.n_src, self.src.shape[1], self.dst.shape[1],
+                                                        self.e_cap, _p(pl.index), _p(pl.edge_query), _p(pl._t_edge), _p(pl.splits), _p(pl._t_splits),
+                                                        _p(self.src), _p(self.dst), _p(pl.e_dev), _p(self.flag), _stream()),
+                    "gaot_union_compose_indexed")
+        elif self.raw:
             L.check(L.load().gaot_union_compose_raw(_p(self.table), self.B, self.n_dst, self.n_src, self.src.shape[1], self.dst.shape[1], self.e_cap,
                                                     _p(pl.index), _p(pl.edge_query), _p(pl.splits), _p(self.src), _p(self.dst), _p(pl.e_dev), _p(self.flag),
                                                     _stream()), "gaot_union_compose_raw")

@@ -354,11 +354,11 @@ def _bind_pairs(step, store, batch_size: int, conditional_norm: bool, forward_kw
     step._pairs = (store, torch.zeros(B, dtype=torch.int32, device=dev), cond)
 
 
-def _load_pair_indices(pairs, indices, who: str):
+def _load_pair_indices(pairs, indices, who: str, binder: str = "bind_pairs"):
     """copy B indices into the step's static list: device to device for a device tensor (a slice of store.epoch_indices()), one small
     upload for a host list"""
     if pairs is None:
-        raise RuntimeError(f"{who}: bind_pairs() first")
+        raise RuntimeError(f"{who}: {binder}() first")
     idx = pairs[1]
     src = indices.reshape(-1) if torch.is_tensor(indices) else torch.tensor([int(i) for i in indices], dtype=torch.int32)
     if src.numel() != idx.numel():
@@ -378,6 +378,66 @@ def _compose_pairs(pairs, x: torch.Tensor, y: torch.Tensor):
     y.copy_(out[1])
     if cond is not None:
         cond.copy_(out[2])
+
+
+class IndexedGraphs(list):
+    """what a step bound by bind_samples hands the model as `encoder_nbrs` / `decoder_nbrs`: the batch's graphs are named by the step's
+    device index list, there are no per-sample lists -- a forward that asks for one left the static-union path (a model in evaluation mode
+    under TrainStep, GAOT_VX_STATIC=0)"""
+
+    def __getitem__(self, i):
+        raise RuntimeError("gaot_amd: an index-driven batch (bind_samples) reached a path that needs per-sample neighbour lists; it runs on "
+                           "static unions only (training mode under TrainStep, EvalStep, GAOT_VX_STATIC on)")
+
+
+def _bind_samples(step, store, batch_size: int, forward_kwargs: Dict):
+    """TrainStep.bind_samples / EvalStep.bind_samples: static x / y (/ xcoord) buffers of the store's shapes, a static index list and --
+    vx -- one static union per scale and side bound to the store's part tables and to that list"""
+    B = int(batch_size)
+    if B < 1:
+        raise ValueError("bind_samples: batch_size must be at least 1")
+    for k in ("xcoord", "encoder_nbrs", "decoder_nbrs"):
+        if store.vx and k in forward_kwargs:
+            raise ValueError(f"bind_samples: `{k}` comes from the store (vx: coordinates and graphs of the indexed samples), not from the caller")
+    if not store.vx and "xcoord" in forward_kwargs:
+        raise ValueError("bind_samples: `xcoord` comes from the store (coord=), not from the caller")
+    dev = store.device
+    x = torch.zeros(B, store.N, store.Cc, dtype=torch.float32, device=dev)
+    y = torch.zeros(B, store.N, store.U, dtype=torch.float32, device=dev)
+    idx = torch.zeros(B, dtype=torch.int32, device=dev)
+    kw = dict(forward_kwargs)
+    if not store.vx:
+        step.bind(x, y, xcoord=store.coord, **kw)
+        if step._vx:
+            raise RuntimeError("bind_samples: an fx store bound as vx")
+        step._samples = (store, idx, None)
+        return
+    enc, dec = getattr(step.model, "encoder", None), getattr(step.model, "decoder", None)
+    if not all(hasattr(m, "vx_unions_indexed") for m in (enc, dec)):
+        raise RuntimeError("bind_samples: the model has no MAGNO encoder / decoder to compose indexed unions for")
+    g = store.graphs
+    latent = forward_kwargs.get("latent_tokens_coord")
+    if not torch.is_tensor(latent):
+        raise ValueError("bind_samples: latent_tokens_coord is required")
+    if latent.device != dev or tuple(latent.shape) != tuple(g.latent.shape) or not torch.equal(latent.detach().float(), g.latent):
+        raise ValueError("bind_samples: latent_tokens_coord differs from the latent grid the GraphStore's graphs were built against")
+    # the conditions bind() checks for a vx step, and the capacities (refused from 2^31 on), before anything is allocated: no silent fallback
+    unions = (enc.vx_unions_indexed(g, idx, B), dec.vx_unions_indexed(g, idx, B))
+    step.bind(x, y, xcoord=torch.zeros(B, store.N, g.dim, dtype=torch.float32, device=dev), encoder_nbrs=IndexedGraphs(), decoder_nbrs=IndexedGraphs(),
+              **kw)
+    if not step._vx:
+        raise RuntimeError("bind_samples: the model does not take a vx batch on static unions (precompute_edges=True, no node_embedding, "
+                           "GAOT_VX_STATIC on, no query_coord)")
+    step._vx = False                  # no per-step table upload, no bucket to pick: the unions below serve every batch of the store
+    step._vx_unions = unions
+    step._samples = (store, idx, step._kwargs["xcoord"])
+    store._watch(unions[0] + unions[1])
+
+
+def _compose_samples(samples, x: torch.Tensor, y: torch.Tensor):
+    """the batch of the step's index list into its static buffers: ONE launch on the GPU (capturable), torch indexing on a CPU store"""
+    store, idx, xcoord = samples
+    store.compose(idx, x, y, xcoord)
 
 
 class _Cuts:
@@ -460,6 +520,7 @@ class TrainStep:
         self._vx_unions = None
         self._graph_sets: Dict = {}
         self._pairs = None            # bind_pairs: (PairStore, static index list [B], static condition [B, 1] or None)
+        self._samples = None          # bind_samples: (SampleStore, static index list [B], static xcoord [B, N, d] or None)
         self.n_captures = 0           # captures made so far (a capture = the step's whole set of graphs)
         self._cuts: Optional[_Cuts] = None
         self._checked_phases = False
@@ -478,6 +539,8 @@ class TrainStep:
         self.bucket.clear()
         if self._pairs is not None:           # bind_pairs: this step's batch is composed from the resident trajectories, inside the capture
             _compose_pairs(self._pairs, self._x, self._y)
+        if self._samples is not None:         # bind_samples: gathered from the resident dataset; the unions' refresh() reads the same index list
+            _compose_samples(self._samples, self._x, self._y)
         if self._vx_unions is not None:       # vx: the unions' tables were uploaded by _vx_load(); the forward only refreshes (capturable)
             self.model.encoder._vx_preloaded = (self._vx_unions[0], self._kwargs["encoder_nbrs"])
             self.model.decoder._vx_preloaded = (self._vx_unions[1], self._kwargs["decoder_nbrs"])
@@ -647,6 +710,7 @@ class TrainStep:
         self._graph_sets = {}
         self._vx_unions = None
         self._pairs = None
+        self._samples = None
         xc = forward_kwargs.get("xcoord")
         self._vx = bool(torch.is_tensor(xc) and xc.dim() == 3 and xc.is_cuda and forward_kwargs.get("encoder_nbrs") is not None
                         and forward_kwargs.get("decoder_nbrs") is not None and forward_kwargs.get("query_coord") is None
@@ -735,6 +799,23 @@ class TrainStep:
         """one training step on the items `indices` (batch_size flat dataset indices: a device tensor, e.g. a slice of
         `store.epoch_indices()`, copied device to device; or a host list); `store.status()` tells whether any was out of range"""
         _load_pair_indices(self._pairs, indices, "TrainStep.step_pairs")
+        return self._step()
+
+    def bind_samples(self, store, batch_size: int, **forward_kwargs):
+        """Static (time-independent) training fed from a `static.SampleStore`, fx or vx: the step owns a static index list [batch_size]; at
+        the head of the forward it gathers c, u (and, vx, the coordinates) of the indexed samples from the resident dataset and -- vx --
+        composes the batch's unions from the store's part tables by the same list, all inside the captured graph.  `step_samples(indices)`
+        only copies `batch_size` indices and replays: one capture for a whole shuffled epoch, no table upload, no per-sample Python, no
+        edge bucket to pick (the unions have the capacity of the store's worst batch: GraphStore.batch_edge_capacity).  `forward_kwargs`:
+        latent_tokens_coord (vx: the grid the store's graphs were built against) and, fx, optional encoder_nbrs / decoder_nbrs.  vx needs
+        what bind() needs for a vx step (precompute_edges, no node_embedding, static unions on) and raises where that fails.  Static
+        shapes mean WHOLE batches.  `bind()` puts the step back on caller-supplied batches."""
+        _bind_samples(self, store, batch_size, forward_kwargs)
+
+    def step_samples(self, indices) -> torch.Tensor:
+        """one training step on the samples `indices` (batch_size sample indices: a device tensor, e.g. a slice of
+        `store.epoch_indices()`, copied device to device; or a host list); `store.status()` tells whether any was out of range"""
+        _load_pair_indices(self._samples, indices, "TrainStep.step_samples", "bind_samples")
         return self._step()
 
     def step(self, pndata: Optional[torch.Tensor] = None, target: Optional[torch.Tensor] = None, xcoord: Optional[torch.Tensor] = None,
@@ -826,6 +907,7 @@ class EvalStep:
         self._vx_unions = None
         self._graph_sets: Dict = {}
         self._pairs = None            # bind_pairs: (PairStore, static index list [B], static condition [B, 1] or None)
+        self._samples = None          # bind_samples: (SampleStore, static index list [B], static xcoord [B, N, d] or None)
         self._scratch: Dict = {}      # this step's own loss partials (ops.scratch_owner)
 
     @property
@@ -844,6 +926,7 @@ class EvalStep:
         self._graph_sets = {}
         self._vx_unions = None
         self._pairs = None
+        self._samples = None
         xc = forward_kwargs.get("xcoord")
         enc, dec = getattr(self.model, "encoder", None), getattr(self.model, "decoder", None)
         self._vx = bool(torch.is_tensor(xc) and xc.dim() == 3 and xc.is_cuda and forward_kwargs.get("encoder_nbrs") is not None
@@ -878,6 +961,8 @@ class EvalStep:
             with torch.no_grad(), ops.replayable_eval():
                 if self._pairs is not None:           # bind_pairs: this step's batch is composed from the resident trajectories, inside the capture
                     _compose_pairs(self._pairs, self._x, self._y)
+                if self._samples is not None:         # bind_samples: gathered from the resident dataset; the unions' refresh() reads the same list
+                    _compose_samples(self._samples, self._x, self._y)
                 if self._vx_unions is not None:       # vx: the tables were uploaded by _vx_load(); the forward only re-composes (capturable)
                     self.model.encoder._vx_preloaded = (self._vx_unions[0], self._kwargs["encoder_nbrs"])
                     self.model.decoder._vx_preloaded = (self._vx_unions[1], self._kwargs["decoder_nbrs"])
@@ -942,6 +1027,16 @@ class EvalStep:
     def step_pairs(self, indices) -> torch.Tensor:
         """one evaluation step on the items `indices` (a device tensor, copied device to device, or a host list); no re-capture"""
         _load_pair_indices(self._pairs, indices, "EvalStep.step_pairs")
+        return self._step()
+
+    def bind_samples(self, store, batch_size: int, **forward_kwargs):
+        """validation batches of a static run gathered from a `static.SampleStore` inside the captured step: TrainStep.bind_samples' rules
+        (static index list, fx or vx, whole batches only)"""
+        _bind_samples(self, store, batch_size, forward_kwargs)
+
+    def step_samples(self, indices) -> torch.Tensor:
+        """one evaluation step on the samples `indices` (a device tensor, copied device to device, or a host list); no re-capture"""
+        _load_pair_indices(self._samples, indices, "EvalStep.step_samples", "bind_samples")
         return self._step()
 
     def _step(self) -> torch.Tensor:

@@ -743,6 +743,30 @@ int gaot_graph_store_fill(const float* xs, int32_t S, int32_t N, const float* la
                           int32_t* dec_index32, int32_t* enc_edge_query, int32_t* dec_edge_query, int32_t* enc_t_edge,
                           int32_t* dec_t_edge, void* scratch, int64_t* sort_scratch, gaot_stream_t stream);
 
+/* ---- static (time-independent) training batches driven by a DEVICE list of sample indices (additions within ABI 10) -----------------
+ * The reference's static trainer (static_trainer.py:160-202) takes c, u and -- vx -- the coordinates and the per-sample graphs of every
+ * item from its datasets on the host and uploads the collated batch per step.  With the dataset resident (graphs.GraphStore,
+ * static.SampleStore) nothing about a batch but its shape is a launch argument of the two entry points below: a captured step replays
+ * with new indices.  Both clamp an index outside [0, S) and OR 1 into *status_flag (only ever OR-ed into: the caller zeroes it).
+ *
+ * gaot_union_compose_indexed: gaot_union_compose for batch entries all_parts[idx[b]], b < n_parts, of a table of S entries that
+ *   describes the whole dataset.  e_begin of the table is NOT read: every workgroup takes the exclusive prefix sum of the indexed
+ *   e_count in LDS.  Outputs, pads and sizes as gaot_union_compose.  A batch whose edge count exceeds e_cap (a list that repeats
+ *   samples, under a capacity sized for distinct ones) ORs 4 into *status_flag and is cut at e_cap: *e_real = e_cap, row splits cut
+ *   there, transposed edge ids cut at e_cap - 1 -- every stored entry names a slot of the array it indexes, nothing is read or
+ *   written outside the tables' arrays and the outputs.
+ *
+ * gaot_sample_gather: x[b] = c[idx[b]] ([N, Cc] blocks of c [S, N, Cc]), y[b] = u[idx[b]] ([N, U]) and, with xs / xcoord given (both or
+ *   neither), xcoord[b] = xs[idx[b]] ([N, D]) in one launch; fp32, contiguous, copied as stored.  16-byte accesses where a block is a
+ *   whole number of them and source and destination are 16-byte aligned, single floats otherwise.  Slab offsets are 64-bit; one [N,
+ *   width] block must stay below 2^31 elements, B <= 65535. */
+int gaot_union_compose_indexed(const gaot_union_part* all_parts_dev, int32_t S, const int32_t* idx_dev, int32_t n_parts, int32_t q_each,
+                               int32_t n_src_each, int32_t dim_src, int32_t dim_dst, int32_t e_cap, int32_t* index32, int32_t* edge_query,
+                               int32_t* t_edge, int32_t* splits32, int32_t* t_splits, float* src, float* dst, int32_t* e_real,
+                               int32_t* status_flag, gaot_stream_t stream);
+int gaot_sample_gather(const float* c, const float* u, const float* xs, int32_t S, int32_t N, int32_t Cc, int32_t U, int32_t D,
+                       const int32_t* idx, int32_t B, float* x, float* y, float* xcoord, int32_t* status_flag, gaot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
