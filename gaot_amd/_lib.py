@@ -162,7 +162,7 @@ PROTOTYPES = {
     "gaot_gno_lift_edge_grad_parts": (C.c_int32, [C.c_int32, C.c_int32]),
     "gaot_gno_lift_edge_grad": (C.c_int, [_f, _f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _f, C.c_int32, _f, _f, _f, _s]),
     "gaot_gno_proj_gather_reduce": (C.c_int, [_f, _f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _f, C.c_int32, _f, _f, _s]),
-    "gaot_gno_proj_backward": (C.c_int, [_f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _f, C.c_int32, _f, _f, _f, _f, _f, _f, _s]),
+    "gaot_gno_proj_backward": (C.c_int, [_f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _f, C.c_int32, _f, _f, _f, _f, _f, _f, _f, _s]),
     "gaot_kernel_mlp_fwd": (C.c_int, [_f, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32, _f, _s]),
     "gaot_debug_set_kernel_mlp_ablate": (C.c_int, [C.c_int]),
     "gaot_debug_set_kernel_mlp_split": (C.c_int, [C.c_int]),
@@ -192,6 +192,9 @@ PROTOTYPES = {
     "gaot_grad_norm_dev": (C.c_int, [_f, C.c_int64, _f, C.c_void_p, _f, _f, C.c_int32, _f, _s]),
     "gaot_adamw_apply_clipped_dev": (C.c_int, [_f, _f, _f, _f, C.c_int64, _f, _f, _f, _f, _s]),
     "gaot_debug_set_ep_chunk": (C.c_int, [C.c_int]),
+    "gaot_debug_set_grouped_helpers": (C.c_int, [C.c_int]),
+    "gaot_debug_set_proj_fold_split": (C.c_int, [C.c_int]),
+    "gaot_debug_set_proj_bwd_rowbias": (C.c_int, [C.c_int]),
     "gaot_gno_ep_workspace": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "gaot_gno_lift_gather_reduce_ep": (C.c_int, [_f, _f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i, _i, _i, C.c_int32, C.c_int32, _f, _f, _f, _i, _s]),
     "gaot_gno_proj_gather_t_ep": (C.c_int, [_f, _f, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i, _i, C.c_int32, _i, _i, _f, _f, _f, _i, _s]),

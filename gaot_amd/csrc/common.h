@@ -266,4 +266,13 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 }  // namespace gaot
 
 // grid size for grid-stride kernels: ceil(n / per) workgroups, at least 1, at most cap
+// out[i] = x[i] + x[RN + i] + ... + x[(B - 1) RN + i], the terms in that order, for i = first, first + step, ... below RN: ONE loop for
+// batchsum_kernel and for the workgroups appended to proj_edge_grad_kernel (gno.hip)
+__device__ __forceinline__ void batchsum_span(const float* __restrict__ x, int B, long RN, float* __restrict__ out, long first, long step) {
+    for (long i = first; i < RN; i += step) {
+        float s = 0.f;
+        for (int b = 0; b < B; ++b) s += x[(long)b * RN + i];
+        out[i] = s;
+    }
+}
 static inline int cap_blocks(long n, int per, int cap) { long b = (n + per - 1) / per; return (int)(b > cap ? cap : (b < 1 ? 1 : b)); }

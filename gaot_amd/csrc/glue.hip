@@ -548,7 +548,58 @@ __global__ __launch_bounds__(256) void proj_fold_fwd_kernel(const float* __restr
     }
 }
 
+// ---- the sums of the backward's small matrices, ONE function each for both forms of the kernel below (the same additions in the same order)
+// acc0 + p[0] + p[stride] + ... (n terms, left to right); AHEAD terms are loaded before the first of them is added
+template <int AHEAD>
+__device__ __forceinline__ float pf_chain(const float* p, long stride, int n, float acc) {
+    int k = 0;
+    if (AHEAD > 1) {
+        for (; k + AHEAD <= n; k += AHEAD) {
+            float v[AHEAD];
+#pragma unroll
+            for (int u = 0; u < AHEAD; ++u) v[u] = __builtin_nontemporal_load(p + (long)(k + u) * stride);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < AHEAD; ++u) acc += v[u];
+        }
+    }
+#pragma unroll 8
+    for (; k < n; ++k) acc += __builtin_nontemporal_load(p + (long)k * stride);
+    return acc;
+}
+// one stretch [j0, j1) of (g_weff Wr_a^T)[o, cc].  The roundings are spelled out, so that they do not depend on what the compiler makes of
+// the loop around the call: they are those of the loop as it has always been compiled (unrolled by 8 behind a remainder loop) -- the first
+// n mod 8 terms fused multiply-adds, the rest in groups of 8 separately rounded products added in order.
+__device__ __forceinline__ float pf_dhw_stretch(const float* __restrict__ g_weff, const float* __restrict__ wa, long lda, int Cout, int o, int cc,
+                                                int j0, int j1) {
+    const float* __restrict__ gp = g_weff + (long)o * Cout;
+    const float* __restrict__ wp = wa + cc * lda;
+    float acc = 0.f;
+    int j = j0;
+    for (const int e = j0 + ((j1 > j0 ? j1 - j0 : 0) & 7); j < e; ++j) acc = __builtin_fmaf(gp[j], wp[j], acc);          // (a stretch past Cout is empty)
+    for (; j < j1; j += 8) {
+        float pr[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) pr[u] = __fmul_rn(gp[j + u], wp[j + u]);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc = __fadd_rn(acc, pr[u]);
+    }
+    return acc;
+}
+// (W^T g_weff)[cc, j]: a chain of fused multiply-adds over the output channels (one channel: the rounded product)
 template <int OC>
+__device__ __forceinline__ float pf_dwa_item(const float* __restrict__ hw, long ldh, const float* __restrict__ g_weff, int Cout, int cc, int j) {
+    float acc = 0.f;
+#pragma unroll
+    for (int o = 0; o < OC; ++o) acc = __builtin_fmaf(hw[o * ldh + cc], g_weff[(long)o * Cout + j], acc);
+    return acc;
+}
+
+// SPLIT (default): what does not depend on the partial rows -- dwa = W^T g_weff and the stretch sums of g_weff Wr_a^T -- is computed in
+// slices by all workgroups ahead of the ticket (the stretch sums go to the workspace behind the partial rows); the last workgroup only
+// adds the partial rows, 16 loads in flight, and joins the two terms of dhw.  false: all of it by the last workgroup, as before
+// (gaot_debug_set_proj_fold_split).  The same sums in the same order either way.
+template <int OC, bool SPLIT>
 __global__ __launch_bounds__(256) void proj_fold_bwd_kernel(const float* __restrict__ g_weff, const float* __restrict__ g_rproj,
                                                             const float* __restrict__ hw, long ldh, const float* __restrict__ wa, long lda,
                                                             const float* __restrict__ rowb, long ldr, int Q, int C, int Cout,
@@ -609,6 +660,21 @@ __global__ __launch_bounds__(256) void proj_fold_bwd_kernel(const float* __restr
         for (int rr = 0; rr < rpb; ++rr) acc += red[rr * W + i];
         ws[(long)blockIdx.x * W + i] = acc;
     }
+    float* ws2 = ws + (long)gridDim.x * W;          // [stretch][OC * C]: the stretch sums of g_weff Wr_a^T (SPLIT)
+    if (SPLIT) {
+        if (dwa)
+            for (int i = blockIdx.x * 256 + threadIdx.x; i < C * Cout; i += gridDim.x * 256) {
+                const int cc = i / Cout, j = i % Cout;
+                dwa[cc * ld_dwa + j] = pf_dwa_item<OC>(hw, ldh, g_weff, Cout, cc, j);
+            }
+        if (dhw) {
+            const int items = OC * C, segs = items >= 256 ? 1 : 256 / items, per = (Cout + segs - 1) / segs;
+            for (int q = blockIdx.x * 256 + threadIdx.x; q < items * segs; q += gridDim.x * 256) {
+                const int i = q % items, sg = q / items;
+                ws2[q] = pf_dhw_stretch(g_weff, wa, lda, Cout, i / C, i % C, sg * per, min(Cout, (sg + 1) * per));
+            }
+        }
+    }
     // the last workgroup to get here adds the partial rows in workgroup order and finishes the small matrices
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -620,6 +686,7 @@ __global__ __launch_bounds__(256) void proj_fold_bwd_kernel(const float* __restr
         if (last) {
             __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         last_s = last;
     }
@@ -633,11 +700,7 @@ __global__ __launch_bounds__(256) void proj_fold_bwd_kernel(const float* __restr
         for (int i0 = 0; i0 < W; i0 += cols) {
             const int i = i0 + (int)threadIdx.x % cols, sg = (int)threadIdx.x / cols;
             float acc = 0.f;
-            if (i < W && sg < segs) {
-                const int b1 = min(nb, (sg + 1) * per);
-#pragma unroll 8
-                for (int b = sg * per; b < b1; ++b) acc += __builtin_nontemporal_load(ws + (long)b * W + i);
-            }
+            if (i < W && sg < segs) acc = pf_chain<SPLIT ? 16 : 1>(ws + (long)(sg * per) * W + i, W, min(nb, (sg + 1) * per) - sg * per, 0.f);
             __syncthreads();
             part[threadIdx.x] = acc;
             __syncthreads();
@@ -649,18 +712,22 @@ __global__ __launch_bounds__(256) void proj_fold_bwd_kernel(const float* __restr
         }
     }
     __syncthreads();
+    if (dhb && threadIdx.x < OC) dhb[threadIdx.x] = red[OC * C + threadIdx.x];
+    if (SPLIT) {
+        if (dhw) {
+            const int items = OC * C, segs = items >= 256 ? 1 : 256 / items;
+            for (int i = threadIdx.x; i < items; i += 256)          // (g_rproj^T rowb)[o, c], then the stretches of (g_weff Wr_a^T)[o, c] in their order
+                dhw[(i / C) * ld_dhw + (i % C)] = pf_chain<4>(ws2 + i, items, segs, red[i]);
+        }
+        return;
+    }
     if (dhw) {
         const int items = OC * C;
         const int segs = items >= 256 ? 1 : 256 / items, cols = 256 / segs, per = (Cout + segs - 1) / segs;
         for (int i0 = 0; i0 < items; i0 += cols) {
             const int i = i0 + (int)threadIdx.x % cols, sg = (int)threadIdx.x / cols;
             float acc = 0.f;
-            if (i < items && sg < segs) {
-                const int o = i / C, cc = i % C;
-                const int j1 = min(Cout, (sg + 1) * per);
-#pragma unroll 8
-                for (int j = sg * per; j < j1; ++j) acc += g_weff[(long)o * Cout + j] * wa[cc * lda + j];      // g_weff Wr_a^T
-            }
+            if (i < items && sg < segs) acc = pf_dhw_stretch(g_weff, wa, lda, Cout, i / C, i % C, sg * per, min(Cout, (sg + 1) * per));      // g_weff Wr_a^T
             __syncthreads();
             part[threadIdx.x] = acc;
             __syncthreads();
@@ -671,23 +738,23 @@ __global__ __launch_bounds__(256) void proj_fold_bwd_kernel(const float* __restr
             }
         }
     }
-    if (dhb && threadIdx.x < OC) dhb[threadIdx.x] = red[OC * C + threadIdx.x];
     if (dwa)
         for (int i = threadIdx.x; i < C * Cout; i += 256) {
             const int cc = i / Cout, j = i % Cout;
-            float acc = 0.f;
-#pragma unroll
-            for (int o = 0; o < OC; ++o) acc += hw[o * ldh + cc] * g_weff[(long)o * Cout + j];       // W^T g_weff
-            dwa[cc * ld_dwa + j] = acc;
+            dwa[cc * ld_dwa + j] = pf_dwa_item<OC>(hw, ldh, g_weff, Cout, cc, j);       // W^T g_weff
         }
 }
 }  // namespace gaot
 
+// A/B switch (gaot_debug_set_proj_fold_split): 1 (default) = proj_fold_bwd_kernel<OC, true>, 0 = the earlier tail; the same bits either way
+static int g_pf_split = 1;
+extern "C" int gaot_debug_set_proj_fold_split(int on) { const int old = g_pf_split; g_pf_split = on ? 1 : 0; return old; }
 static inline int pf_pow2_ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 static inline int pf_blocks(int Q, int rpb) { int nb = (Q + rpb - 1) / rpb; return nb > 256 ? 256 : (nb < 1 ? 1 : nb); }
 extern "C" int32_t gaot_proj_fold_workspace(int32_t Q, int32_t C, int32_t out_channels) {
     const int lanes = pf_pow2_ceil(C / 4 > 0 ? C / 4 : 1), rpb = 256 / (lanes < 256 ? lanes : 256);
-    return pf_blocks(Q, rpb > 0 ? rpb : 1) * (out_channels * C + out_channels);
+    const int items = out_channels * C;          // + the stretch sums of g_weff Wr_a^T (proj_fold_bwd_kernel, SPLIT)
+    return pf_blocks(Q, rpb > 0 ? rpb : 1) * (out_channels * C + out_channels) + items * (items >= 256 ? 1 : 256 / (items > 0 ? items : 1));
 }
 static int pf_check(const char* who, int32_t Q, int32_t C, int32_t Cout, int32_t OC, const float* hw, int64_t ldh, const float* wa, const float* rowb, int64_t ldr) {
     GAOT_REQUIRE(Q > 0 && C > 0 && C % 4 == 0 && C <= 256 && Cout > 0 && Cout <= 1024 && OC >= 1 && OC <= 4, "%s: need Q > 0, C %% 4 == 0, C <= 256, 1 <= out_channels <= 4", who);
@@ -718,8 +785,10 @@ extern "C" int gaot_proj_fold_bwd(const float* g_weff, const float* g_rproj, con
     const int nb = pf_blocks(Q, rpb);
     const size_t lds = sizeof(float) * (size_t)rpb * (out_channels * C + out_channels);
     GAOT_REQUIRE(lds <= 60 * 1024, "proj_fold_bwd: C = %d too wide for the workgroup reduction", C);
-#define PF(OC) hipLaunchKernelGGL((gaot::proj_fold_bwd_kernel<OC>), dim3(nb), dim3(256), lds, ST(stream), g_weff, g_rproj, hw, (long)ldh, wa, (long)lda, rowb, (long)ldr, \
-                                  Q, C, Cout, drowb, dhw, (long)ld_dhw, dhb, dwa, (long)ld_dwa, workspace, ticket, lanes)
+#define PF(OC) do { if (g_pf_split) hipLaunchKernelGGL((gaot::proj_fold_bwd_kernel<OC, true>), dim3(nb), dim3(256), lds, ST(stream), g_weff, g_rproj, hw, (long)ldh, wa, (long)lda, \
+                                                     rowb, (long)ldr, Q, C, Cout, drowb, dhw, (long)ld_dhw, dhb, dwa, (long)ld_dwa, workspace, ticket, lanes); \
+                    else hipLaunchKernelGGL((gaot::proj_fold_bwd_kernel<OC, false>), dim3(nb), dim3(256), lds, ST(stream), g_weff, g_rproj, hw, (long)ldh, wa, (long)lda, \
+                                            rowb, (long)ldr, Q, C, Cout, drowb, dhw, (long)ld_dhw, dhb, dwa, (long)ld_dwa, workspace, ticket, lanes); } while (0)
     if (out_channels == 1) PF(1); else if (out_channels == 2) PF(2); else if (out_channels == 3) PF(3); else PF(4);
 #undef PF
     GAOT_CHECK_LAUNCH("gaot_proj_fold_bwd");

@@ -1108,14 +1108,21 @@ __global__ __launch_bounds__(256) void proj_gather_reduce_kernel(const float* __
 }
 
 // per edge row: T_o[e,:] = a_e sum_b dY[b,q,o] f[b,j,:];  dk[e,:] = sum_o weff[o,:] T_o;  dweff[o,:] += k[e,:] T_o (partials)
+// The first `nb` workgroups of the grid walk the edges.  Any workgroups behind them (drowb != NULL) compute the row-bias gradient, the
+// sum of dY over the batch: it depends on dY alone and used to be a launch of its own (gaot_batchsum: the same loop, batchsum_span).
 template <int OC>
 __global__ __launch_bounds__(256) void proj_edge_grad_kernel(const float* __restrict__ dy, const float* __restrict__ k,
                                                              const float* __restrict__ f, const float* __restrict__ weff, int B,
                                                              int Q, int n_src, int C, const int* __restrict__ idx,
                                                              const int* __restrict__ eq, int E, const float* __restrict__ escale,
                                                              float* __restrict__ dk, float* __restrict__ part, int lanes_per_row,
-                                                             int rows_per_block, const int* __restrict__ order) {
+                                                             int rows_per_block, const int* __restrict__ order, int nb,
+                                                             float* __restrict__ drowb) {
     extern __shared__ __attribute__((aligned(16))) float red[];      // [rows_per_block][OC * C]
+    if ((int)blockIdx.x >= nb) {
+        batchsum_span(dy, B, (long)Q * OC, drowb, (long)((int)blockIdx.x - nb) * 256 + threadIdx.x, (long)((int)gridDim.x - nb) * 256);
+        return;
+    }
     const int row = threadIdx.x / lanes_per_row;
     const int c = (threadIdx.x % lanes_per_row) * 4;
     const bool cok = c < C;
@@ -1131,10 +1138,10 @@ __global__ __launch_bounds__(256) void proj_edge_grad_kernel(const float* __rest
     // i.e. spatially random) every edge pulled its B rows through the fabric again: 99 MB per launch for 8 MB of features (PMC).
     int lb;
     {
-        const int nb = gridDim.x, q8 = nb >> 3, r8 = nb & 7, x = blockIdx.x & 7, slot = blockIdx.x >> 3;
+        const int q8 = nb >> 3, r8 = nb & 7, x = blockIdx.x & 7, slot = blockIdx.x >> 3;
         lb = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + slot;
     }
-    const int per = ((E + (int)gridDim.x * rows_per_block - 1) / ((int)gridDim.x * rows_per_block)) * rows_per_block;     // positions per workgroup
+    const int per = ((E + nb * rows_per_block - 1) / (nb * rows_per_block)) * rows_per_block;     // positions per workgroup
     const int i_end = min(E, (lb + 1) * per);
     for (int i = lb * per + row; i < i_end && cok; i += rows_per_block) {
         const int e = order ? order[i] : i;
@@ -1277,10 +1284,15 @@ extern "C" int gaot_gno_proj_gather_reduce(const float* k, const float* f, const
     return GAOT_OK;
 }
 
+// A/B switch: 1 (default) = the row-bias gradient inside the edge-gradient launch, 0 = by gaot_batchsum behind it; the same bits either way
+static int g_proj_bwd_rowbias = 1;
+extern "C" int gaot_debug_set_proj_bwd_rowbias(int on) { const int old = g_proj_bwd_rowbias; g_proj_bwd_rowbias = on ? 1 : 0; return old; }
+
 extern "C" int gaot_gno_proj_backward(const float* dy, const float* k, const float* f, const float* weff, int32_t B, int32_t Q,
                                       int32_t n_src, int32_t C, int32_t out_channels, const int32_t* index32,
                                       const int32_t* edge_query, int32_t E, const int32_t* t_splits, const int32_t* t_edge,
-                                      const float* escale, float* dk, float* dweff_partial, float* df, gaot_stream_t stream) {
+                                      const float* escale, float* dk, float* dweff_partial, float* df, float* drowbias,
+                                      gaot_stream_t stream) {
     if (int rc = proj_check(B, C, out_channels)) return rc;
     GAOT_REQUIRE(E > 0 && dy && k && f && weff && index32 && edge_query && dk && dweff_partial && aligned16(k) && aligned16(f) && aligned16(weff) &&
                  aligned16(dk), "gno_proj_backward: E > 0 and non-null 16-byte aligned operands required");
@@ -1288,8 +1300,12 @@ extern "C" int gaot_gno_proj_backward(const float* dy, const float* k, const flo
     const int nb = gaot_gno_lift_edge_grad_parts(E, C);
     const size_t lds = sizeof(float) * (size_t)rpb * out_channels * C;
     GAOT_REQUIRE(lds <= 64 * 1024, "gno_proj_backward: C = %d too wide for the workgroup reduction", C);
-#define PE(OC) hipLaunchKernelGGL((proj_edge_grad_kernel<OC>), dim3(nb), dim3(256), lds, ST(stream), dy, k, f, weff, B, Q, n_src, C, index32, \
-                                  edge_query, E, escale, dk, dweff_partial, lpr, rpb, t_edge)
+    // the row-bias gradient [Q, OC] in workgroups appended to the grid (the grid of gaot_batchsum, capped lower: they run beside the edge
+    // walk); switched off (gaot_debug_set_proj_bwd_rowbias), the launch of its own that it used to be
+    float* const drb_in = g_proj_bwd_rowbias ? drowbias : nullptr;
+    const int nx = drb_in ? cap_blocks((long)Q * out_channels, 256, 256) : 0;
+#define PE(OC) hipLaunchKernelGGL((proj_edge_grad_kernel<OC>), dim3(nb + nx), dim3(256), lds, ST(stream), dy, k, f, weff, B, Q, n_src, C, index32, \
+                                  edge_query, E, escale, dk, dweff_partial, lpr, rpb, t_edge, nb, drb_in)
     if (out_channels == 1) PE(1); else if (out_channels == 2) PE(2); else if (out_channels == 3) PE(3); else PE(4);
 #undef PE
     if (df) {
@@ -1301,6 +1317,7 @@ extern "C" int gaot_gno_proj_backward(const float* dy, const float* k, const flo
 #undef PT
     }
     GAOT_CHECK_LAUNCH("gaot_gno_proj_backward");
+    if (drowbias && !drb_in) return gaot_batchsum(dy, B, (int64_t)Q * out_channels, drowbias, stream);
     return GAOT_OK;
 }
 

@@ -263,25 +263,43 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restri
     __syncthreads();
     if (wave == 0 && n < N) out[n] = red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane];
 }
-// short matrices (M <= 1024 rows, e.g. per-workgroup partial rows): ONE launch; 16 columns per workgroup as 4 float4
-// lanes x 64 row groups (N / 16 workgroups: the matrix is tiny, parallelism comes from splitting the columns finely),
-// four independent 16-byte loads in flight per thread, fixed-order LDS sum
-__global__ __launch_bounds__(256) void colsum_small_kernel(const float* __restrict__ x, int M, int N, float* __restrict__ out) {
-    __shared__ f32x4 red[64][4];
-    const int c4 = threadIdx.x & 3, rg = threadIdx.x >> 2;
-    const int n = blockIdx.x * 16 + c4 * 4;
-    f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
-    if (n < N) {
-        int r = rg;
-        for (; r + 192 < M; r += 256) {
-            s0 += *reinterpret_cast<const f32x4*>(x + (long)r * N + n);
-            s1 += *reinterpret_cast<const f32x4*>(x + (long)(r + 64) * N + n);
-            s2 += *reinterpret_cast<const f32x4*>(x + (long)(r + 128) * N + n);
-            s3 += *reinterpret_cast<const f32x4*>(x + (long)(r + 192) * N + n);
-        }
-        for (; r < M; r += 64) s0 += *reinterpret_cast<const f32x4*>(x + (long)r * N + n);
+// ---- grouped launches (column sums, fp16 planes, absmax): the item table travels in the kernel arguments, every item owns the
+// workgroups up to its wg_end.  The item of a workgroup is the first whose wg_end exceeds its index: found by binary search (6 or 7
+// dependent scalar loads; the scan the column-sum and plane kernels used to do is one dependent scalar load per item passed, up to 64)
+template <typename Item>
+__device__ __forceinline__ int group_item_search(const Item* it, int n, int wg) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (wg >= it[mid].wg_end) lo = mid + 1; else hi = mid;
     }
-    red[rg][c4] = (s0 + s1) + (s2 + s3);
+    return lo;
+}
+template <typename Item>
+__device__ __forceinline__ int group_item_scan(const Item* it, int n, int wg) {
+    int i = 0;
+    while (i + 1 < n && wg >= it[i].wg_end) ++i;
+    return i;
+}
+
+// ---- column sums of short matrices, 16 columns per workgroup as 4 float4 lanes x 64 row groups.  ONE summation for every kernel that
+// uses the tiling: a thread owns the rows rg, rg + 64, ... of its float4 column and deals them round-robin to four accumulators (four
+// independent 16-byte loads in flight), joined as (s0 + s1) + (s2 + s3); colsum_tile_join adds the 64 row groups in a fixed LDS tree.
+__device__ __forceinline__ f32x4 colsum_tile_rows(const float* __restrict__ x, long ld, int M, int n, int rg) {
+    f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
+    int r = rg;
+    for (; r + 192 < M; r += 256) {
+        s0 += *reinterpret_cast<const f32x4*>(x + (long)r * ld + n);
+        s1 += *reinterpret_cast<const f32x4*>(x + (long)(r + 64) * ld + n);
+        s2 += *reinterpret_cast<const f32x4*>(x + (long)(r + 128) * ld + n);
+        s3 += *reinterpret_cast<const f32x4*>(x + (long)(r + 192) * ld + n);
+    }
+    for (; r < M; r += 64) s0 += *reinterpret_cast<const f32x4*>(x + (long)r * ld + n);
+    return (s0 + s1) + (s2 + s3);
+}
+// every thread of the workgroup calls it with its row group's sum; the total of float4 column c4 comes back in the threads of row group 0
+__device__ __forceinline__ f32x4 colsum_tile_join(f32x4 (*red)[4], f32x4 s, int rg, int c4) {
+    red[rg][c4] = s;
     __syncthreads();
     if (rg < 4) {                      // 4 threads per float4 column: 16 row groups each, then a 2-step exchange
         f32x4 t = red[rg][c4];
@@ -290,56 +308,51 @@ __global__ __launch_bounds__(256) void colsum_small_kernel(const float* __restri
         red[rg][c4] = t;
     }
     __syncthreads();
-    if (rg == 0 && n < N) *reinterpret_cast<f32x4*>(out + n) = (red[0][c4] + red[1][c4]) + (red[2][c4] + red[3][c4]);
+    return (red[0][c4] + red[1][c4]) + (red[2][c4] + red[3][c4]);
+}
+// short matrices (M <= 1024 rows, e.g. per-workgroup partial rows): ONE launch; N / 16 workgroups (the matrix is tiny, parallelism comes
+// from splitting the columns finely)
+__global__ __launch_bounds__(256) void colsum_small_kernel(const float* __restrict__ x, int M, int N, float* __restrict__ out) {
+    __shared__ f32x4 red[64][4];
+    const int c4 = threadIdx.x & 3, rg = threadIdx.x >> 2;
+    const int n = blockIdx.x * 16 + c4 * 4;
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    if (n < N) s = colsum_tile_rows(x, N, M, n, rg);
+    const f32x4 t = colsum_tile_join(red, s, rg, c4);
+    if (rg == 0 && n < N) *reinterpret_cast<f32x4*>(out + n) = t;
 }
 // ---- grouped column sums: ONE launch over many small partial-row matrices (the per-workgroup partial rows of the norm-weight
-// and lifting gradients: each used to cost its own 5 us launch at the end of its backward node).  Same tiling as colsum_small_kernel
-// (16 columns per workgroup as 4 float4 lanes x 64 row groups, fixed-order LDS sum); the item table travels in the kernel arguments.
+// and lifting gradients: each used to cost its own 5 us launch at the end of its backward node).  Same tiling and summation as
+// colsum_small_kernel.  PAIRED (default): the item by table search, and tiles placed so that the two halves of a 128-byte line meet in
+// one L2 (below); false: the earlier launch (gaot_debug_set_grouped_helpers).  Every tile is summed by the same code either way.
 constexpr int COLSUM_GROUP_MAX = 64;       // 64 x 56 B of table in the kernel arguments
 struct ColsumItem { const float* x; float* out; long ld; int M, N, wg_end, out_cols; long out_ld; };
 struct ColsumGroupArgs { int n; ColsumItem it[COLSUM_GROUP_MAX]; };
+template <bool PAIRED>
 __global__ __launch_bounds__(256) void colsum_grouped_kernel(const ColsumGroupArgs g) {
     __shared__ f32x4 red[64][4];
-    int i = 0;
-    while (i + 1 < g.n && (int)blockIdx.x >= g.it[i].wg_end) ++i;
+    const int i = PAIRED ? group_item_search(g.it, g.n, (int)blockIdx.x) : group_item_scan(g.it, g.n, (int)blockIdx.x);
     const int first = i > 0 ? g.it[i - 1].wg_end : 0;
-    const float* __restrict__ x = g.it[i].x;
-    const long ld = g.it[i].ld;
-    const int M = g.it[i].M, N = g.it[i].N;
+    const int N = g.it[i].N;
     const int c4 = threadIdx.x & 3, rg = threadIdx.x >> 2;
-    const int n = ((int)blockIdx.x - first) * 16 + c4 * 4;
-    f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
-    if (n < N) {
-        int r = rg;
-        for (; r + 192 < M; r += 256) {
-            s0 += *reinterpret_cast<const f32x4*>(x + (long)r * ld + n);
-            s1 += *reinterpret_cast<const f32x4*>(x + (long)(r + 64) * ld + n);
-            s2 += *reinterpret_cast<const f32x4*>(x + (long)(r + 128) * ld + n);
-            s3 += *reinterpret_cast<const f32x4*>(x + (long)(r + 192) * ld + n);
-        }
-        for (; r < M; r += 64) s0 += *reinterpret_cast<const f32x4*>(x + (long)r * ld + n);
-    }
-    red[rg][c4] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (rg < 4) {
-        f32x4 t = red[rg][c4];
-#pragma unroll
-        for (int q = 1; q < 16; ++q) t += red[rg + 4 * q][c4];
-        red[rg][c4] = t;
-    }
-    __syncthreads();
+    int tile = (int)blockIdx.x - first;
+    // a workgroup reads 64 bytes of every row: half a 128-byte line, whose other half belongs to the next tile.  Consecutive workgroups go
+    // to different XCDs (private L2s), so every line was fetched twice (FETCH_SIZE: 77 MB for 37 MB of partial rows, no L2 hits); within
+    // whole groups of 16 tiles, workgroups w and w + 8 -- the same XCD -- now take the two halves of a line (40 MB, every second request
+    // a hit).  Placement only: every tile is summed as before, by some workgroup.
+    if (PAIRED && tile < (((N + 15) >> 4) & ~15)) tile = (tile & ~15) | ((tile & 7) << 1) | ((tile >> 3) & 1);
+    const int n = tile * 16 + c4 * 4;
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    if (n < N) s = colsum_tile_rows(g.it[i].x, g.it[i].ld, g.it[i].M, n, rg);
+    const f32x4 t = colsum_tile_join(red, s, rg, c4);
     if (rg == 0 && n < N) {
         const int oc = g.it[i].out_cols;          // the sums form an [N / oc, oc] matrix stored with row stride out_ld (oc = N: one row)
         float* dst = g.it[i].out + (long)(n / oc) * g.it[i].out_ld + (n % oc);
-        *reinterpret_cast<f32x4*>(dst) = (red[0][c4] + red[1][c4]) + (red[2][c4] + red[3][c4]);
+        *reinterpret_cast<f32x4*>(dst) = t;
     }
 }
 __global__ void batchsum_kernel(const float* __restrict__ x, int B, long RN, float* __restrict__ out) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < RN; i += (long)gridDim.x * blockDim.x) {
-        float s = 0.f;
-        for (int b = 0; b < B; ++b) s += x[(long)b * RN + i];
-        out[i] = s;
-    }
+    batchsum_span(x, B, RN, out, (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
 }
 
 // ---------------------------------------------------------------- patchify (gaot.py:182-185,202-205,224-231)
@@ -576,6 +589,12 @@ __global__ void patchify_vec_kernel(const float* __restrict__ in, float* __restr
 using namespace gaot;
 #define ST(s) reinterpret_cast<hipStream_t>(s)
 
+// A/B switch of the grouped helper launches (gaot_debug_set_grouped_helpers), one bit per kernel: 1 = absmax (gap-free matrices of any
+// width as one flat stream, one atomic per workgroup), 2 = fp16 planes (table search, 16-byte tile loads), 4 = grouped column sums
+// (table search, the two halves of a line on one XCD).  A cleared bit launches the earlier kernel; the results are the same bits either way.
+static int g_grouped_helpers = 7;
+extern "C" int gaot_debug_set_grouped_helpers(int bits) { const int old = g_grouped_helpers; g_grouped_helpers = bits & 7; return old; }
+
 extern "C" int gaot_rmsnorm_fwd(const float* x, const float* w, int32_t M, int32_t D, float eps, float* y, float* rstd, float* y_absmax,
                                 gaot_stream_t stream) {
     GAOT_REQUIRE(x && w && y && rstd && M > 0 && D > 0, "rmsnorm_fwd: bad arguments");
@@ -684,7 +703,8 @@ extern "C" int gaot_colsum_grouped(const gaot_colsum_item* items, int32_t n, gao
             wg += cdiv(it.N, 16);
             a.it[i] = ColsumItem{it.x, it.out, (long)it.ld, it.M, it.N, wg, it.out_cols > 0 ? it.out_cols : it.N, it.out_cols > 0 ? (long)it.out_ld : (long)it.N};
         }
-        hipLaunchKernelGGL(colsum_grouped_kernel, dim3(wg), dim3(256), 0, ST(stream), a);
+        if (g_grouped_helpers & 4) hipLaunchKernelGGL(colsum_grouped_kernel<true>, dim3(wg), dim3(256), 0, ST(stream), a);
+        else hipLaunchKernelGGL(colsum_grouped_kernel<false>, dim3(wg), dim3(256), 0, ST(stream), a);
         GAOT_CHECK_LAUNCH("gaot_colsum_grouped");
     }
     return GAOT_OK;
@@ -697,10 +717,12 @@ extern "C" int gaot_colsum_grouped(const gaot_colsum_item* items, int32_t n, gao
 constexpr int F16PL_GROUP_MAX = 64;
 struct F16PlItem { const float* src; const float* amax; unsigned short* pk; unsigned short* pt; long ld; int rows, cols, tiles_c, wg_end; };
 struct F16PlGroupArgs { int n; F16PlItem it[F16PL_GROUP_MAX]; };
+// WIDE (default): the item by table search, the tile by 16-byte loads where the matrix allows (four per thread instead of sixteen 4-byte
+// ones); false: the earlier launch (gaot_debug_set_grouped_helpers).  The tile in LDS, and all that follows, is the same either way.
+template <bool WIDE>
 __global__ __launch_bounds__(256) void split_f16_planes_kernel(const F16PlGroupArgs g) {
     __shared__ float tile[64][65];
-    int i = 0;
-    while (i + 1 < g.n && (int)blockIdx.x >= g.it[i].wg_end) ++i;
+    const int i = WIDE ? group_item_search(g.it, g.n, (int)blockIdx.x) : group_item_scan(g.it, g.n, (int)blockIdx.x);
     const int local = (int)blockIdx.x - (i > 0 ? g.it[i - 1].wg_end : 0);
     const int r0 = (local / g.it[i].tiles_c) * 64, c0 = (local % g.it[i].tiles_c) * 64;
     const int rows = g.it[i].rows, cols = g.it[i].cols;
@@ -709,9 +731,19 @@ __global__ __launch_bounds__(256) void split_f16_planes_kernel(const F16PlGroupA
     const int tid = threadIdx.x;
     float sc, inv;
     amax_scale(g.it[i].amax, sc, inv);
-    for (int e = tid; e < 64 * 64; e += 256) {
-        const int r = e >> 6, c = e & 63;
-        tile[r][c] = (r0 + r < rows && c0 + c < cols) ? src[(long)(r0 + r) * ld + c0 + c] : 0.f;
+    if (WIDE && (ld & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 15u) == 0) {
+#pragma unroll
+        for (int e = tid; e < 64 * 16; e += 256) {          // cols is a multiple of 16 (checked on the host): a quad lies inside or outside
+            const int r = e >> 4, c = (e & 15) * 4;
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (r0 + r < rows && c0 + c < cols) v = *reinterpret_cast<const f32x4*>(src + (long)(r0 + r) * ld + c0 + c);
+            tile[r][c] = v[0]; tile[r][c + 1] = v[1]; tile[r][c + 2] = v[2]; tile[r][c + 3] = v[3];
+        }
+    } else {
+        for (int e = tid; e < 64 * 64; e += 256) {
+            const int r = e >> 6, c = e & 63;
+            tile[r][c] = (r0 + r < rows && c0 + c < cols) ? src[(long)(r0 + r) * ld + c0 + c] : 0.f;
+        }
     }
     __syncthreads();
     // the matrix's spread for the consumers (gemm_split.hip, "Dynamic range of the fp16 pieces"): L = log2(scaled tensor maximum / geometric
@@ -777,20 +809,46 @@ __global__ __launch_bounds__(256) void split_f16_planes_kernel(const F16PlGroupA
 constexpr int ABSMAX_GROUP_MAX = 96;
 struct AbsmaxItem { const float* x; float* out; long ld; int rows, cols, wg_end; };
 struct AbsmaxGroupArgs { int n; AbsmaxItem it[ABSMAX_GROUP_MAX]; };
+// FLAT (default): every matrix stored without gaps is one flat stream, whatever its width and alignment -- a bias vector arrives as [n, 1]
+// and a norm weight likewise, and the row-per-wave walk below gave such an item to ONE lane of each wave, n / 4 dependent loads long: the
+// launch lasted as long as the longest vector, not as long as the weights take to stream -- and a workgroup publishes ONE atomic (all
+// workgroups of the launch finish together: amax_publish_block).  false: the earlier launch (gaot_debug_set_grouped_helpers).  The maximum
+// over the word's slots is the same either way.
+template <bool FLAT>
 __global__ __launch_bounds__(256) void absmax_grouped_kernel(const AbsmaxGroupArgs g) {
-    int lo_ = 0, hi_ = g.n - 1;                      // first item whose wg_end exceeds this workgroup's index (binary search: the table
-    while (lo_ < hi_) {                              // sits in the kernel arguments, a linear scan is ~90 dependent scalar loads)
-        const int mid = (lo_ + hi_) >> 1;
-        if ((int)blockIdx.x >= g.it[mid].wg_end) lo_ = mid + 1; else hi_ = mid;
-    }
-    const int i = lo_;
+    __shared__ float amred[4];
+    const int i = group_item_search(g.it, g.n, (int)blockIdx.x);
     const int first = i > 0 ? g.it[i - 1].wg_end : 0, nwg = g.it[i].wg_end - first, b = (int)blockIdx.x - first;
     const float* __restrict__ x = g.it[i].x;
     const long ld = g.it[i].ld;
     const int rows = g.it[i].rows, cols = g.it[i].cols;
     float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f;
     const bool vec = (cols & 3) == 0 && (ld & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) & 15u) == 0);
-    if (vec && ld == cols) {                     // contiguous: one flat stream of float4, four in flight per thread
+    if (FLAT && (ld == cols || rows == 1)) {
+        // up to three floats ahead of the first 16-byte boundary and up to three behind the last whole float4: threads of the item's first workgroup
+        const long total = (long)rows * cols;
+        const long lead = (long)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(x) & 15u)) & 15u) >> 2);
+        const long head = lead < total ? lead : total, n4 = (total - head) >> 2, rest = total - head - 4 * n4;
+        const long step = (long)nwg * 256;
+        const f32x4* __restrict__ x4 = reinterpret_cast<const f32x4*>(x + head);
+        long idx = (long)b * 256 + threadIdx.x;
+        for (; idx + 3 * step < n4; idx += 4 * step) {
+            const f32x4 v0 = x4[idx], v1 = x4[idx + step], v2 = x4[idx + 2 * step], v3 = x4[idx + 3 * step];
+            m0 = fmaxf(m0, fmaxf(fmaxf(fabsf(v0[0]), fabsf(v0[1])), fmaxf(fabsf(v0[2]), fabsf(v0[3]))));
+            m1 = fmaxf(m1, fmaxf(fmaxf(fabsf(v1[0]), fabsf(v1[1])), fmaxf(fabsf(v1[2]), fabsf(v1[3]))));
+            m2 = fmaxf(m2, fmaxf(fmaxf(fabsf(v2[0]), fabsf(v2[1])), fmaxf(fabsf(v2[2]), fabsf(v2[3]))));
+            m3 = fmaxf(m3, fmaxf(fmaxf(fabsf(v3[0]), fabsf(v3[1])), fmaxf(fabsf(v3[2]), fabsf(v3[3]))));
+        }
+        for (; idx < n4; idx += step) {
+            const f32x4 v0 = x4[idx];
+            m0 = fmaxf(m0, fmaxf(fmaxf(fabsf(v0[0]), fabsf(v0[1])), fmaxf(fabsf(v0[2]), fabsf(v0[3]))));
+        }
+        if (b == 0) {
+            const long t = threadIdx.x;
+            if (t < head) m1 = fmaxf(m1, fabsf(x[t]));
+            else if (t - head < rest) m1 = fmaxf(m1, fabsf(x[head + 4 * n4 + (t - head)]));
+        }
+    } else if (vec && ld == cols) {              // contiguous: one flat stream of float4, four in flight per thread
         const long total = (long)rows * (cols >> 2), step = (long)nwg * 256;
         const f32x4* __restrict__ x4 = reinterpret_cast<const f32x4*>(x);
         long idx = (long)b * 256 + threadIdx.x;
@@ -817,7 +875,8 @@ __global__ __launch_bounds__(256) void absmax_grouped_kernel(const AbsmaxGroupAr
         for (long r = (long)b * 4 + wave; r < rows; r += (long)nwg * 4)
             for (int c = lane; c < cols; c += 64) m0 = fmaxf(m0, fabsf(x[r * ld + c]));
     }
-    amax_publish(g.it[i].out, fmaxf(fmaxf(m0, m1), fmaxf(m2, m3)), threadIdx.x & 63, (int)blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (FLAT) amax_publish_block<4>(g.it[i].out, fmaxf(fmaxf(m0, m1), fmaxf(m2, m3)), amred);
+    else amax_publish(g.it[i].out, fmaxf(fmaxf(m0, m1), fmaxf(m2, m3)), threadIdx.x & 63, (int)blockIdx.x * 4 + (threadIdx.x >> 6));
 }
 
 extern "C" int gaot_split_f16_planes_grouped(const gaot_f16_planes_item* items, int32_t n, gaot_stream_t stream) {
@@ -839,7 +898,8 @@ extern "C" int gaot_split_f16_planes_grouped(const gaot_f16_planes_item* items, 
             a.it[i] = F16PlItem{it.src, it.absmax, reinterpret_cast<unsigned short*>(it.planes_k), reinterpret_cast<unsigned short*>(it.planes_t),
                                 (long)it.ld, it.rows, it.cols, tc, wg};
         }
-        hipLaunchKernelGGL(split_f16_planes_kernel, dim3(wg), dim3(256), 0, ST(stream), a);
+        if (g_grouped_helpers & 2) hipLaunchKernelGGL(split_f16_planes_kernel<true>, dim3(wg), dim3(256), 0, ST(stream), a);
+        else hipLaunchKernelGGL(split_f16_planes_kernel<false>, dim3(wg), dim3(256), 0, ST(stream), a);
         GAOT_CHECK_LAUNCH("gaot_split_f16_planes_grouped");
     }
     return GAOT_OK;
@@ -860,7 +920,8 @@ extern "C" int gaot_absmax_grouped(const gaot_absmax_item* items, int32_t n, gao
             wg += (int)(w > 1024 ? 1024 : (w < 1 ? 1 : w));
             a.it[i] = AbsmaxItem{it.x, it.out, (long)it.ld, it.rows, it.cols, wg};
         }
-        hipLaunchKernelGGL(absmax_grouped_kernel, dim3(wg), dim3(256), 0, ST(stream), a);
+        if (g_grouped_helpers & 1) hipLaunchKernelGGL(absmax_grouped_kernel<true>, dim3(wg), dim3(256), 0, ST(stream), a);
+        else hipLaunchKernelGGL(absmax_grouped_kernel<false>, dim3(wg), dim3(256), 0, ST(stream), a);
         GAOT_CHECK_LAUNCH("gaot_absmax_grouped");
     }
     return GAOT_OK;

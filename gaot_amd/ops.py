@@ -1852,9 +1852,11 @@ class _GNOProjTransform(torch.autograd.Function):
             # the edge-partitioned dF kernel keeps four samples' sums per lane group (every k row read once per four samples): also
             # ahead of the row-parallel form on regular plans once the batch is that large (C2: 24.6 -> 18.9 us, tools/gno_c2_kernels.py)
             ep = df is not None and (_GNO_EP == 1 or (_GNO_EP == 2 and (plan.t_rows_skewed or B >= 4)))
+            if rb_shape is not None and need[3]:          # the sum of dy over the batch: workgroups appended to the edge-gradient launch
+                drowb = torch.empty(rb_shape, device=k.device, dtype=torch.float32)
             L.check(lib.gaot_gno_proj_backward(_p(dy), _p(k), _p(f), _p(weff), B, plan.Q, n_src, Cc, OC, _p(plan.index),
                                                _p(plan.edge_query), plan.E, _p(plan.t_splits), _p(plan.t_edge),
-                                               _p(esc) if has_e else None, _p(dk), _p(part), None if ep else _p(df), _stream()),
+                                               _p(esc) if has_e else None, _p(dk), _p(part), None if ep else _p(df), _p(drowb), _stream()),
                     "gaot_gno_proj_backward")
             if ep:      # dF over the (skewed) transposed CSR: edge-partitioned, segmented
                 ws = torch.empty(int(lib.gaot_gno_ep_workspace(plan.E, Cc, B)), device=k.device, dtype=torch.float32)
@@ -1864,7 +1866,7 @@ class _GNOProjTransform(torch.autograd.Function):
                                                         _p(plan.e_dev), _p(ow), _stream()), "gaot_gno_proj_gather_t_ep_w")
                 _publish(ow, df)
             dweff = colsum(part).reshape(OC, Cc)
-        if rb_shape is not None and need[3]:
+        if rb_shape is not None and need[3] and drowb is None:
             drowb = batchsum(dy.reshape(B, -1), B).reshape(rb_shape)
         if has_bias and need[4]:
             dbias = colsum(dy.reshape(-1, OC))

@@ -87,6 +87,17 @@ int gaot_debug_set_kernel_mlp_ablate(int bits);
  * kernels.  Same results to fp32 rounding either way.  Returns the previous value. */
 int gaot_debug_set_kernel_mlp_split(int on);
 int gaot_debug_set_ep_chunk(int edges_per_chunk);      /* tuning only: 0 = default (32) */
+/* A/B hook: the grouped helper launches (gaot_absmax_grouped, gaot_split_f16_planes_grouped, gaot_colsum_grouped), one bit per kernel:
+ * 1 = absmax, 2 = fp16 planes, 4 = column sums; 7 (default) = the present kernels, a cleared bit = the kernel as it was before them.
+ * Same bits in every output either way (the absmax word: the same maximum over its slots).  Returns the previous value. */
+int gaot_debug_set_grouped_helpers(int bits);
+/* A/B hook: gaot_proj_fold_bwd, 1 (default) = dwa and the stretch sums of g_weff Wr_a^T computed in slices by every workgroup ahead of the
+ * ticket, the last workgroup only adds the partial rows and joins dhw; 0 = all of it by the last workgroup, as before.  Same bits either
+ * way.  Returns the previous value. */
+int gaot_debug_set_proj_fold_split(int on);
+/* A/B hook: gaot_gno_proj_backward with a row-bias gradient, 1 (default) = computed by workgroups appended to the edge-gradient launch,
+ * 0 = by a gaot_batchsum launch behind it, as before.  Same bits either way.  Returns the previous value. */
+int gaot_debug_set_proj_bwd_rowbias(int on);
 
 #ifdef __cplusplus
 }

@@ -31,7 +31,7 @@ part = torch.empty(int(lib.gaot_gno_lift_edge_grad_parts(plan.E, C)), OC * C, de
 ws = torch.empty(int(lib.gaot_gno_ep_workspace(plan.E, C, B)), device=dev)
 def bwd(with_df):
     L.check(lib.gaot_gno_proj_backward(_p(dy), _p(k), _p(f), _p(weff), B, plan.Q, n_src, C, OC, _p(plan.index), _p(plan.edge_query), plan.E,
-                                       _p(plan.t_splits), _p(plan.t_edge), _p(esc), _p(dk), _p(part), _p(df) if with_df else None, _stream()), "bwd")
+                                       _p(plan.t_splits), _p(plan.t_edge), _p(esc), _p(dk), _p(part), _p(df) if with_df else None, None, _stream()), "bwd")
 def t_ep():
     L.check(lib.gaot_gno_proj_gather_t_ep(_p(k), _p(dy), _p(weff), B, plan.Q, n_src, C, OC, _p(plan.index), _p(plan.edge_query), plan.E,
                                           _p(plan.t_splits), _p(plan.t_edge), _p(esc), _p(df2), _p(ws), None, _stream()), "t_ep")

@@ -3,7 +3,7 @@
 switch of gaot_amd.ops):
     python tools/step_ab.py gaot_debug_set_gemm_ad 0 1 [2 ...]
 builds one TrainStep per value (the graph is captured with the switch set), then times them in alternation (3 rounds x 60 steps each)
-and prints ms per step per value.  --c4: the 4 096-token batch of BASELINE configs[3] instead."""
+and prints ms per step per value.  Several library switches moved together: join their names with `+` (each gets the value).  --c4: the 4 096-token batch of BASELINE configs[3] instead."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -17,6 +17,11 @@ if args[0].startswith("ops."):          # a module-level switch of gaot_amd.ops 
     _name = args[0][4:]
     def fn(v):
         old = getattr(ops, _name); setattr(ops, _name, v); return old
+elif "+" in args[0]:                    # several library switches moved together (every one gets the value): a+b+c 0 7
+    _fns = [getattr(lib, n) for n in args[0].split("+")]
+    def fn(v):
+        olds = [f(o) for f, o in zip(_fns, v if isinstance(v, list) else [v] * len(_fns))]
+        return olds
 else:
     fn = getattr(lib, args[0])
 values = [int(v) for v in args[1:]]
