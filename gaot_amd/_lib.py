@@ -71,6 +71,20 @@ class UnionPartRaw(C.Structure):
     _fields_ = [("index", _i), ("splits", _i), ("src", _f), ("dst", _f), ("e_begin", C.c_int32), ("e_count", C.c_int32), ("reserved", C.c_int64 * 3)]
 
 
+class AttentionQuery(C.Structure):
+    """gaot_debug_attention_query: an attention call as gaot_debug_attention_plan reads it (facts: the GAOT_ATTN_FACT_* bits)"""
+    _fields_ = [("B", C.c_int32), ("S", C.c_int32), ("H", C.c_int32), ("Hkv", C.c_int32), ("head_dim", C.c_int32), ("pieces", C.c_int32),
+                ("direction", C.c_int32), ("dropout", C.c_int32), ("facts", C.c_uint32)]
+
+
+ATTENTION_PLAN_COLUMNS = ["delta", "delta_grid", "family", "nw", "dh", "pp", "op", "f16", "ks", "tr", "qs", "var", "drop", "grid", "block", "lds_bytes",
+                          "keys_per_wg", "n_kblocks", "combine_grid", "add_cols_grid", "reduce", "reduce_dp4", "reduce_grid", "absmax_tensors",
+                          "o_part", "lse_part", "delta_off", "dq_part", "dk2", "dv2", "workspace_floats"]
+ATTENTION_FACTS = ["qkv_absmax", "dout_absmax", "dqkv_absmax", "vec", "o_aligned", "ldo4", "workspace", "ws_aligned", "dq_aligned", "dk_aligned",
+                   "dv_aligned", "lddq4", "lddk4", "lddv4", "dq_part_aligned"]          # bit i of AttentionQuery.facts
+ATTENTION_FAMILIES = ["OneKey", "Wide", "Fp32", "Glds", "Split", "Pipe", "BwdSplit4", "BwdSplitDh", "BwdSplit8", "BwdH16", "BwdSplit8Dh"]
+
+
 class ColsumItem(C.Structure):
     """gaot_colsum_item: out[n] = sum_m x[m * ld + n]"""
     _fields_ = [("x", _f), ("ld", C.c_int64), ("out", _f), ("M", C.c_int32), ("N", C.c_int32), ("out_cols", C.c_int32), ("out_ld", C.c_int64)]
@@ -174,6 +188,8 @@ PROTOTYPES = {
     "gaot_debug_set_attention_p_pieces": (C.c_int, [C.c_int]),
     "gaot_debug_set_attention_operand_pieces": (C.c_int, [C.c_int]),
     "gaot_debug_set_attention_tr": (C.c_int, [C.c_int]),
+    "gaot_debug_attention_plan": (C.c_int, [C.POINTER(AttentionQuery), C.POINTER(C.c_int64)]),
+    "gaot_debug_last_attention_plan": (C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
     "gaot_kernel_mlp_fwd_w": (C.c_int, [_f, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32), C.c_int32, _f, _s]),
     "gaot_kernel_mlp_bwd_w": (C.c_int, [_f, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_int32),

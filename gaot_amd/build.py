@@ -12,7 +12,7 @@ SOURCES = ["capi.cpp", "gemm.hip", "gemm_glds.hip", "gemm_split.hip", "gemm_ad.h
 # translation units added since: kept in a list of their own because tests/test_eval_metrics_cpu.py pins len(SOURCES) at the sixteen above
 DATA_SOURCES = ["seq_pairs.hip", "graph_store.hip", "sample_store.hip"]
 ALL_SOURCES = SOURCES + DATA_SOURCES
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "segsort.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_plan.h"), os.path.join(CSRC, "attention_common.h"), os.path.join(HERE, "..", "include", "gaot_hip.h"), os.path.join(HERE, "..", "include", "gaot_hip_debug.h")]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "segsort.h"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "gemm_plan.h"), os.path.join(CSRC, "attention_common.h"), os.path.join(CSRC, "attention_plan.h"), os.path.join(HERE, "..", "include", "gaot_hip.h"), os.path.join(HERE, "..", "include", "gaot_hip_debug.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-array-bounds"] + os.environ.get("GAOT_HIPCC_EXTRA", "").split()      # (extra: A/B builds, tools)
 
 

@@ -12,6 +12,7 @@
 // (ds_read_b128 on +4-padded rows for A operands, row-contiguous ds_read_b32 otherwise).
 // Everything is deterministic: no atomics; dQ partials per key block are reduced in a fixed order.
 #include "attention_common.h"
+#include "attention_plan.h"
 
 namespace gaot {
 
@@ -2798,10 +2799,6 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_split8_dh_kernel(const AttnAr
     if (F16 && p.dqkv_amax) { __syncthreads(); amax_publish_block<8>(p.dqkv_amax, am * (float)QS, reinterpret_cast<float*>(smem)); }
 }
 
-template <int DP> static size_t bwd_lds_bytes() {
-    return sizeof(float) * (2 * 32 * (DP + 4) + 64 + 4 * 32 * DP + 4 * 32 * 33 + 4 * 32 * (DP < 64 ? DP : 64));
-}
-
 // a[r][c] += a2[r][c], b[r][c] += b2[r][c] over [rows][4 c4]: a, b pitched column blocks (dK / dV inside the fused dqkv buffer), a2, b2 dense
 // (the second half's partials of the query-split backward)
 __global__ void attn_add_cols_kernel(float* a, long lda, const float* a2, float* b, long ldb, const float* b2, long rows, int c4) {
@@ -2831,139 +2828,252 @@ __global__ __launch_bounds__(64) void attn_fwd_one_key_kernel(const AttnArgs p) 
     if (threadIdx.x == 0) p.lse[bh] = acc * p.scale;
 }
 
-static int fill_common(AttnArgs& a, const float* q, const float* k, const float* v, int64_t ldq, int64_t ldk, int64_t ldv,
-                       int B, int S, int H, int Hkv, int D) {
+}  // namespace gaot
+
+// ---- host side: validate, gather the facts, ask attention_plan.h, launch what the plan names
+using namespace gaot;
+#define ST(s) reinterpret_cast<hipStream_t>(s)
+
+static AttnSwitches g_sw;          // the kernel-selection switches (attention_plan.h) behind the gaot_debug_set_attention_* setters
+extern "C" int gaot_debug_set_attention_p_pieces(int n) {
+    const int old = g_sw.p_pieces;
+    g_sw.p_pieces = (n == 33 || n == 22 || n == 23 || n == 32) ? n : (n == 3 ? 33 : (n == 2 ? 22 : FOLLOW_CALL));
+    return old;
+}
+extern "C" int gaot_debug_set_attention_operand_pieces(int n) { const int old = g_sw.operand_pieces; g_sw.operand_pieces = n == 3 ? 3 : (n == 2 ? 2 : FOLLOW_CALL); return old; }
+extern "C" int gaot_debug_set_attention_tr(int on) { const int old = g_sw.tr; g_sw.tr = on != 0; return old; }
+extern "C" int gaot_debug_set_attention_qsplit(int on) { const int old = g_sw.qsplit; g_sw.qsplit = on != 0; return old; }
+extern "C" int gaot_debug_set_attention_pipe(int on) { const int old = g_sw.pipe; g_sw.pipe = on; return old; }
+extern "C" int gaot_debug_set_attention_dh8(int on) { const int old = g_sw.dh8; g_sw.dh8 = on; return old; }
+extern "C" int gaot_debug_set_attention_h16(int nw) { const int old = g_sw.h16; g_sw.h16 = nw; return old; }
+extern "C" int gaot_debug_set_attention_split(int on) { const int old = (int)g_sw.split; g_sw.split = (AttnSplit)on; return old; }
+extern "C" int gaot_debug_set_attention_keysplit(int on) { const int old = (int)g_sw.keysplit; g_sw.keysplit = (AttnKeySplit)on; return old; }
+
+extern "C" int64_t gaot_attention_fwd_workspace(int32_t B, int32_t S, int32_t H, int32_t head_dim) { return attn_fwd_workspace_floats(B, S, H, head_dim, g_sw); }
+extern "C" int64_t gaot_attention_bwd_workspace(int32_t B, int32_t S, int32_t H, int32_t head_dim) { return attn_bwd_workspace_floats(B, S, H, head_dim); }
+
+// the four entry points: what each checks of its sizes, in its own words
+enum AttnEntry { ENTRY_FWD = 0, ENTRY_FWD_DROPOUT = 1, ENTRY_BWD = 2, ENTRY_BWD_DROPOUT = 3 };
+static const char* const ENTRY_NAME[4] = {"attention_fwd", "attention_fwd_dropout", "attention_bwd", "attention_bwd_dropout"};
+static int validate(AttnEntry e, bool pointers, int pieces, int B, int S, int H, int Hkv, int head_dim) {
+    const char* name = ENTRY_NAME[e];
+    GAOT_REQUIRE(pointers, "%s: null pointer", name);
+    if (e == ENTRY_FWD || e == ENTRY_BWD) GAOT_REQUIRE(pieces == 0 || (pieces >= 2 && pieces <= 4), "%s: pieces %d not in {0, 2, 3, 4}", name, pieces);
+    const bool sizes = B > 0 && S > 0 && H > 0 && Hkv > 0 && H % Hkv == 0;
+    if (e == ENTRY_FWD || e == ENTRY_FWD_DROPOUT) GAOT_REQUIRE(sizes, "%s: bad sizes B=%d S=%d H=%d Hkv=%d", name, B, S, H, Hkv);
+    else GAOT_REQUIRE(sizes, "%s: bad sizes", name);
+    GAOT_REQUIRE(head_dim > 0 && head_dim <= 256, "%s: head_dim %d not in 1..256", name, head_dim);
+    return GAOT_OK;
+}
+
+static void fill_common(AttnArgs& a, const float* q, const float* k, const float* v, int64_t ldq, int64_t ldk, int64_t ldv,
+                        int B, int S, int H, int Hkv, int D) {
     a.q = q; a.k = k; a.v = v; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv;
     a.B = B; a.S = S; a.H = H; a.Hkv = Hkv; a.D = D;
     a.scale = 1.0f / sqrtf((float)D);
     a.vec = (D % 4 == 0) && (ldq % 4 == 0) && (ldk % 4 == 0) && (ldv % 4 == 0) && aligned16(q) && aligned16(k) && aligned16(v);
-    return 0;
+}
+static void fill_backward(AttnArgs& a, const float* o, const float* dout, int64_t ldo, const float* lse, float* dq, float* dk, float* dv,
+                          int64_t lddq, int64_t lddk, int64_t lddv) {
+    a.vec = a.vec && (ldo % 4 == 0) && aligned16(dout);
+    a.oin = o; a.dout = dout; a.ldo = ldo; a.lse = const_cast<float*>(lse);
+    a.dq = dq; a.dk = dk; a.dv = dv; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
+}
+static int fill_dropout(AttnArgs& a, float p_drop, const uint64_t* seed) {
+    GAOT_REQUIRE(p_drop > 0.f && p_drop < 1.f && seed, "attention dropout: need 0 < p < 1 and a device seed word");
+    a.drop_seed = reinterpret_cast<const unsigned long long*>(seed);
+    const double keep = 1.0 - (double)p_drop;
+    a.drop_thresh = (unsigned)(keep * 4294967296.0 >= 4294967295.0 ? 4294967295.0 : keep * 4294967296.0);
+    a.drop_scale = (float)(1.0 / keep);
+    return GAOT_OK;
 }
 
-}  // namespace gaot
-
-using namespace gaot;
-#define ST(s) reinterpret_cast<hipStream_t>(s)
-
-static int g_attn_ks = 1;        // [r6] key-split forward (128 .. 255 blocks of 256 queries x batch x heads, with a workspace): 0 = off
-static int g_attn_dh8 = 1;       // [r6] 32 < head_dim <= 64, fp16 pieces: the 8-wave 256-key backward (query-split at 128 .. 255 blocks); 0 = the 4-wave kernel
-static int g_attn_h16 = 0x18;    // [r6] the fp16-piece backward (256-key blocks, one workgroup per key block): 8 + 16 VAR = attn_bwd_h16_kernel<8, 1, VAR> (default VAR 1), 4 = <4>, 0 = attn_bwd_split8_kernel
-static int g_attn_split = 1;     // head_dim 32: 1 = split-bf16 kernels (default; 8-wave forward when it fills the chip), 0 = fp32-MFMA kernels,
-                                 // 2 = split with the 8-wave forward always, 3 = split with the 4-wave forward always
-// pieces of P (forward) and of P / dS (backward) in the head_dim-32 split kernels, as 10 * forward + backward: 22 (default) = two ROUNDED
-// pieces everywhere (five piece products per P V / dS K product instead of six).  Measured at the bench configuration against the
-// oracle evaluated in float64 (tools/grad_errors.py): output 1.25e-7 with either forward, worst gradient tensor 7.6e-7 (q_proj of the
-// middle layer) with either; the kernel alone is 2.2e-6 off float64 instead of 2.4e-7 on random data -- a rounding error of the
-// probabilities, which sum to one and average out over the keys.  33 / 32 / 23: A/B and tests.
-// -1 (default): follow the call's `pieces` argument (3 -> 33, 2 -> 22); anything else overrides every call (A/B runs, tools)
-static int g_attn_pp = -1;
-extern "C" int gaot_debug_set_attention_p_pieces(int n) {
-    const int old = g_attn_pp;
-    g_attn_pp = (n == 33 || n == 22 || n == 23 || n == 32) ? n : (n == 3 ? 33 : (n == 2 ? 22 : -1));
-    return old;
+// the facts of a filled argument block (the one place where pointers become booleans)
+static AttnFacts gather_facts(const AttnArgs& a, AttnDir dir, bool dropout, int pieces, const float* workspace) {
+    AttnFacts f = {};
+    f.B = a.B; f.S = a.S; f.H = a.H; f.Hkv = a.Hkv; f.D = a.D;
+    f.dir = dir; f.dropout = dropout; f.pieces = pieces;
+    f.has_qkv_absmax = a.qkv_amax != nullptr; f.has_dout_absmax = a.dout_amax != nullptr; f.has_dqkv_absmax = a.dqkv_amax != nullptr;
+    f.vec = a.vec;
+    f.ldo4 = a.ldo % 4 == 0;
+    f.has_workspace = workspace != nullptr; f.ws_aligned = aligned16(workspace);
+    if (dir == AttnDir::Forward) { f.o_aligned = aligned16(a.o); return f; }
+    f.o_aligned = aligned16(a.oin);
+    f.dq_aligned = aligned16(a.dq); f.dk_aligned = aligned16(a.dk); f.dv_aligned = aligned16(a.dv);
+    f.lddq4 = a.lddq % 4 == 0; f.lddk4 = a.lddk % 4 == 0; f.lddv4 = a.lddv % 4 == 0;
+    f.dq_part_aligned = aligned16(workspace + attn_bwd_layout(a.B, a.S, a.H, a.D).dq_part);
+    return f;
 }
-// pieces of the Q / K / V / dO operands in the same kernels (with two-piece P / dS only): 2 (default) = two rounded pieces, three piece
-// products per k-step in every product of the kernel (forward 11 -> 6 MFMAs per k-step pair, backward 27 -> 15); 3 = exact three-way splits
-static int g_attn_op = -1;       // -1 (default): follow the call's `pieces` argument
-extern "C" int gaot_debug_set_attention_operand_pieces(int n) { const int old = g_attn_op; g_attn_op = n == 3 ? 3 : (n == 2 ? 2 : -1); return old; }
-static int g_attn_tr = 1;        // 1 (default): the two-piece 8-wave backward takes its transposed operands through transposing LDS reads
-extern "C" int gaot_debug_set_attention_tr(int on) { const int old = g_attn_tr; g_attn_tr = on ? 1 : 0; return old; }
-static int g_attn_qsplit = 1;    // 1 (default): the 8-wave fp16-piece backward shares a key block's query tiles between two workgroups when that fills the chip (A/B switch)
-extern "C" int gaot_debug_set_attention_qsplit(int on) { const int old = g_attn_qsplit; g_attn_qsplit = on ? 1 : 0; return old; }
-static int g_attn_pipe = 0;      // 1 = the software-pipelined 8-wave forward for S % 64 == 0 (same speed as the plain one since both keep the
-                                 // tile product off the running accumulator: 57.6 vs 58.0 us; kept for tools/attn_ablate.hip and as a tested variant)
-extern "C" int gaot_debug_set_attention_pipe(int on) { const int old = g_attn_pipe; g_attn_pipe = on; return old; }
-extern "C" int gaot_debug_set_attention_dh8(int on) { const int old = g_attn_dh8; g_attn_dh8 = on; return old; }
-extern "C" int gaot_debug_set_attention_h16(int nw) { const int old = g_attn_h16; g_attn_h16 = nw; return old; }
-extern "C" int gaot_debug_set_attention_split(int on) { const int old = g_attn_split; g_attn_split = on; return old; }
 
-// key-split forward (attn_fwd_split_kernel<8, 64, .., KS = 2>): shapes it is for -- 128 .. 255 blocks of 256 queries x batch x heads, at least eight
-// key tiles, head_dim 36 .. 64 in steps of 4.  (head_dim 32 stays on the 4-wave kernel, which already runs two workgroups per CU there:
-// 4 x 1 024 x 8 x 32 measured 28.7 us against 30.2 with the split; g_attn_ks = 2 forces it on for the tests.)
-static bool fwd_key_split_shape(int B, int S, int H, int head_dim) {
-    const long wg8 = (long)cdiv(S, 256) * B * H;
-    return g_attn_ks && g_attn_split == 1 && wg8 >= 128 && wg8 < 256 && cdiv(S, 64) >= 8 && head_dim >= (g_attn_ks == 2 ? 32 : 36) && head_dim <= 64 && head_dim % 4 == 0;
-}
-extern "C" int64_t gaot_attention_fwd_workspace(int32_t B, int32_t S, int32_t H, int32_t head_dim) {
-    if (B <= 0 || S <= 0 || H <= 0 || head_dim <= 0) return -1;
-    return fwd_key_split_shape(B, S, H, head_dim) ? 2 * ((int64_t)B * S * H * head_dim + (int64_t)B * H * S) : 0;
-}
-extern "C" int gaot_debug_set_attention_keysplit(int on) { const int old = g_attn_ks; g_attn_ks = on; return old; }
+static thread_local AttnPlan t_last_plan[2];       // what this thread's last forward / backward launch executed
+static thread_local bool t_has_plan[2];
 
-extern "C" int gaot_attention_fwd_ws(const float* q, const float* k, const float* v, int64_t ldq, int64_t ldk, int64_t ldv,
-                                     int32_t B, int32_t S, int32_t H, int32_t Hkv, int32_t head_dim, float* o, int64_t ldo,
-                                     float* lse, int32_t pieces, const float* qkv_absmax, float* workspace, gaot_stream_t stream);
-extern "C" int gaot_attention_fwd(const float* q, const float* k, const float* v, int64_t ldq, int64_t ldk, int64_t ldv,
-                                  int32_t B, int32_t S, int32_t H, int32_t Hkv, int32_t head_dim, float* o, int64_t ldo,
-                                  float* lse, int32_t pieces, const float* qkv_absmax, gaot_stream_t stream) {
-    return gaot_attention_fwd_ws(q, k, v, ldq, ldk, ldv, B, S, H, Hkv, head_dim, o, ldo, lse, pieces, qkv_absmax, nullptr, stream);
+// a kernel whose dynamic LDS exceeds the default limit: raise the limit once per kernel
+template <int DP, bool DROP> static void allow_bwd_lds() {
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<DP, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, attn_bwd_lds_bytes(DP));
+        attr_set = true;
+    }
 }
+
+// template arguments of a plan as one switch label
+static constexpr long tkey(int a, int b = 0, int c = 0, int d = 0, int e = 0, int f = 0) { return (((((long)a * 256 + b) * 256 + c) * 256 + d) * 256 + e) * 256 + f; }
+#define MAIN(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(p.grid), dim3(p.block), p.lds_bytes, ST(stream), a)
+#define ON(key, ...) case key: MAIN(__VA_ARGS__); break
+
+static int attention_forward(AttnArgs& a, const AttnFacts& f, float* workspace, const char* name, gaot_stream_t stream) {
+    const AttnPlan p = plan_attention(f, g_sw);
+    t_last_plan[0] = p; t_has_plan[0] = true;
+    if (p.ks == 2) { a.o_part = workspace + p.o_part; a.lse_part = workspace + p.lse_part; }
+    bool found = true;
+    switch (p.family) {
+        case AttnFamily::OneKey: MAIN(attn_fwd_one_key_kernel); break;
+        case AttnFamily::Wide: attn_wide_fwd_launch(a, p.drop, ST(stream)); break;
+        case AttnFamily::Split:
+            switch (tkey(p.nw, p.dh, p.pp, p.op, p.f16, p.ks)) {
+                ON(tkey(8, 32, 2, 2, 1, 2), attn_fwd_split_kernel<8, 32, 2, 2, true, 2>);
+                ON(tkey(8, 64, 2, 2, 1, 2), attn_fwd_split_kernel<8, 64, 2, 2, true, 2>);
+                ON(tkey(8, 32, 2, 2, 1, 1), attn_fwd_split_kernel<8, 32, 2, 2, true>);
+                ON(tkey(8, 32, 3, 3, 0, 1), attn_fwd_split_kernel<8, 32, 3>);
+                ON(tkey(8, 32, 2, 3, 0, 1), attn_fwd_split_kernel<8, 32, 2>);
+                ON(tkey(8, 32, 2, 2, 0, 1), attn_fwd_split_kernel<8, 32, 2, 2>);
+                ON(tkey(4, 32, 2, 2, 1, 1), attn_fwd_split_kernel<4, 32, 2, 2, true>);
+                ON(tkey(4, 32, 3, 3, 0, 1), attn_fwd_split_kernel<4, 32, 3>);
+                ON(tkey(4, 32, 2, 3, 0, 1), attn_fwd_split_kernel<4, 32, 2>);
+                ON(tkey(4, 32, 2, 2, 0, 1), attn_fwd_split_kernel<4, 32, 2, 2>);
+                ON(tkey(8, 64, 2, 2, 1, 1), attn_fwd_split_kernel<8, 64, 2, 2, true>);
+                ON(tkey(4, 64, 2, 2, 1, 1), attn_fwd_split_kernel<4, 64, 2, 2, true>);
+                ON(tkey(8, 64, 2, 2, 0, 1), attn_fwd_split_kernel<8, 64, 2, 2>);
+                ON(tkey(8, 64, 3, 3, 0, 1), attn_fwd_split_kernel<8, 64>);
+                ON(tkey(4, 64, 2, 2, 0, 1), attn_fwd_split_kernel<4, 64, 2, 2>);
+                ON(tkey(4, 64, 3, 3, 0, 1), attn_fwd_split_kernel<4, 64>);
+                default: found = false;
+            }
+            break;
+        case AttnFamily::Pipe: MAIN(attn_fwd_split_pipe_kernel<0>); break;
+        case AttnFamily::Glds: MAIN(attn_fwd_glds_kernel); break;
+        case AttnFamily::Fp32:
+            switch (tkey(p.dh, p.drop)) {
+                ON(tkey(32, 0), attn_fwd_kernel<32>);
+                ON(tkey(64, 0), attn_fwd_kernel<64>);
+                ON(tkey(128, 0), attn_fwd_kernel<128>);
+                ON(tkey(32, 1), attn_fwd_kernel<32, true>);
+                ON(tkey(64, 1), attn_fwd_kernel<64, true>);
+                ON(tkey(128, 1), attn_fwd_kernel<128, true>);
+                default: found = false;
+            }
+            break;
+        default: found = false;
+    }
+    GAOT_REQUIRE(found, "%s: no kernel for the plan (family %d)", name, (int)p.family);
+    if (p.combine_grid) hipLaunchKernelGGL(attn_fwd_combine_kernel, dim3(p.combine_grid), dim3(256), 0, ST(stream), a);
+    GAOT_CHECK_LAUNCH(p.ks == 2 ? "gaot_attention_fwd_ws" : name);
+    return GAOT_OK;
+}
+
+static int attention_backward(AttnArgs& a, const AttnFacts& f, float* workspace, const char* name, gaot_stream_t stream) {
+    const AttnPlan p = plan_attention(f, g_sw);
+    t_last_plan[1] = p; t_has_plan[1] = true;
+    a.delta = workspace + p.delta_off;
+    a.dq_part = workspace + p.dq_part;
+    a.n_kblocks = p.n_kblocks;
+    if (p.qs == 2) { a.dk2 = workspace + p.dk2; a.dv2 = workspace + p.dv2; }
+    if (p.delta == AttnDelta::Vector) hipLaunchKernelGGL(attn_delta_vec_kernel, dim3(p.delta_grid), dim3(256), 0, ST(stream), a, 8);
+    else if (p.delta == AttnDelta::Scalar) hipLaunchKernelGGL(attn_delta_kernel, dim3(p.delta_grid), dim3(256), 0, ST(stream), a);
+    bool found = true;
+    switch (p.family) {
+        case AttnFamily::Wide: attn_wide_bwd_launch(a, p.drop, ST(stream)); break;
+        case AttnFamily::BwdSplit8:
+            switch (tkey(p.pp, p.op, p.tr, p.f16, p.qs)) {
+                ON(tkey(2, 2, 1, 1, 2), attn_bwd_split8_kernel<2, 2, true, true, 2>);
+                ON(tkey(2, 2, 1, 1, 1), attn_bwd_split8_kernel<2, 2, true, true>);
+                ON(tkey(3, 3, 0, 0, 1), attn_bwd_split8_kernel<3>);
+                ON(tkey(2, 3, 0, 0, 1), attn_bwd_split8_kernel<2>);
+                ON(tkey(2, 2, 1, 0, 1), attn_bwd_split8_kernel<2, 2, true>);
+                ON(tkey(2, 2, 0, 0, 1), attn_bwd_split8_kernel<2, 2>);
+                default: found = false;
+            }
+            break;
+        case AttnFamily::BwdH16:
+            switch (tkey(p.nw, p.qs, p.var)) {
+                ON(tkey(4, 1, 0), attn_bwd_h16_kernel<4>);
+                ON(tkey(8, 1, 1), attn_bwd_h16_kernel<8, 1, 1>);
+                ON(tkey(8, 1, 2), attn_bwd_h16_kernel<8, 1, 2>);
+                ON(tkey(8, 1, 3), attn_bwd_h16_kernel<8, 1, 3>);
+                ON(tkey(8, 1, 0), attn_bwd_h16_kernel<8>);
+                default: found = false;
+            }
+            break;
+        case AttnFamily::BwdSplit4: MAIN(attn_bwd_split_kernel); break;
+        case AttnFamily::BwdSplit8Dh:
+            switch (tkey(p.f16, p.qs)) {
+                ON(tkey(1, 1), attn_bwd_split8_dh_kernel<true, 1>);
+                ON(tkey(1, 2), attn_bwd_split8_dh_kernel<true, 2>);
+                ON(tkey(0, 1), attn_bwd_split8_dh_kernel<false, 1>);
+                default: found = false;
+            }
+            break;
+        case AttnFamily::BwdSplitDh:
+            switch (tkey(p.dh, p.pp, p.op, p.f16)) {
+                ON(tkey(64, 2, 2, 1), attn_bwd_split_dh_kernel<64, 2, 2, true>);
+                ON(tkey(64, 2, 2, 0), attn_bwd_split_dh_kernel<64, 2, 2>);
+                ON(tkey(64, 3, 3, 0), attn_bwd_split_dh_kernel<64>);
+                default: found = false;
+            }
+            break;
+        case AttnFamily::Fp32:
+            switch (tkey(p.dh, p.drop)) {
+                ON(tkey(32, 0), attn_bwd_kernel<32>);
+                case tkey(64, 0): allow_bwd_lds<64, false>(); MAIN(attn_bwd_kernel<64>); break;
+                case tkey(128, 0): allow_bwd_lds<128, false>(); MAIN(attn_bwd_kernel<128>); break;
+                ON(tkey(32, 1), attn_bwd_kernel<32, true>);
+                case tkey(128, 1): allow_bwd_lds<128, true>(); MAIN(attn_bwd_kernel<128, true>); break;
+                case tkey(64, 1): allow_bwd_lds<64, true>(); MAIN(attn_bwd_kernel<64, true>); break;
+                default: found = false;
+            }
+            break;
+        default: found = false;
+    }
+    GAOT_REQUIRE(found, "%s: no kernel for the plan (family %d)", name, (int)p.family);
+    if (p.add_cols_grid) {
+        const int c4 = a.H * a.D / 4;
+        hipLaunchKernelGGL(attn_add_cols_kernel, dim3(p.add_cols_grid), dim3(256), 0, ST(stream), a.dk, (long)a.lddk, a.dk2, a.dv, (long)a.lddv, a.dv2, (long)a.B * a.S, c4);
+    }
+    if (p.reduce == AttnReduce::Vector) {
+        const dim3 g(p.reduce_grid);
+        switch (p.reduce_dp4) {
+            case 8: hipLaunchKernelGGL(attn_dq_reduce_vec_kernel<8>, g, dim3(256), 0, ST(stream), a); break;
+            case 16: hipLaunchKernelGGL(attn_dq_reduce_vec_kernel<16>, g, dim3(256), 0, ST(stream), a); break;
+            default: hipLaunchKernelGGL(attn_dq_reduce_vec_kernel<32>, g, dim3(256), 0, ST(stream), a); break;
+        }
+    } else if (p.reduce == AttnReduce::Scalar) {
+        hipLaunchKernelGGL(attn_dq_reduce_kernel, dim3(p.reduce_grid), dim3(256), 0, ST(stream), a, attn_padded_dim(a.D));
+    }
+    GAOT_CHECK_LAUNCH(name);
+    if (p.absmax_tensors) {        // dK and dV, with dQ in front where the plan says three
+        const gaot_absmax_item it[3] = {{a.dq, a.lddq, a.B * a.S, a.H * a.D, a.dqkv_amax}, {a.dk, a.lddk, a.B * a.S, a.H * a.D, a.dqkv_amax},
+                                        {a.dv, a.lddv, a.B * a.S, a.H * a.D, a.dqkv_amax}};
+        if (int rc = gaot_absmax_grouped(it + 3 - p.absmax_tensors, p.absmax_tensors, stream)) return rc;
+    }
+    return GAOT_OK;
+}
+#undef ON
+#undef MAIN
 
 extern "C" int gaot_attention_fwd_ws(const float* q, const float* k, const float* v, int64_t ldq, int64_t ldk, int64_t ldv,
                                      int32_t B, int32_t S, int32_t H, int32_t Hkv, int32_t head_dim, float* o, int64_t ldo,
                                      float* lse, int32_t pieces, const float* qkv_absmax, float* workspace, gaot_stream_t stream) {
-    GAOT_REQUIRE(q && k && v && o && lse, "attention_fwd: null pointer");
-    GAOT_REQUIRE(pieces == 0 || (pieces >= 2 && pieces <= 4), "attention_fwd: pieces %d not in {0, 2, 3, 4}", pieces);
-    const bool f16 = pieces == 4 && qkv_absmax != nullptr && ::g_attn_pp < 0 && ::g_attn_op < 0;      // fp16 pieces where a kernel takes them; else exact
-    const int g_attn_pp = ::g_attn_pp >= 0 ? ::g_attn_pp : (pieces == 2 ? 22 : 33);
-    const int g_attn_op = ::g_attn_op >= 0 ? ::g_attn_op : (pieces == 2 ? 2 : 3);
-    GAOT_REQUIRE(B > 0 && S > 0 && H > 0 && Hkv > 0 && H % Hkv == 0, "attention_fwd: bad sizes B=%d S=%d H=%d Hkv=%d", B, S, H, Hkv);
-    GAOT_REQUIRE(head_dim > 0 && head_dim <= 256, "attention_fwd: head_dim %d not in 1..256", head_dim);
+    if (int rc = validate(ENTRY_FWD, q && k && v && o && lse, pieces, B, S, H, Hkv, head_dim)) return rc;
     AttnArgs a = {};
     fill_common(a, q, k, v, ldq, ldk, ldv, B, S, H, Hkv, head_dim);
     a.o = o; a.ldo = ldo; a.lse = lse; a.qkv_amax = qkv_absmax;
-    if (S == 1) {                // a single key: out = v exactly, every head_dim, every `pieces`
-        hipLaunchKernelGGL(attn_fwd_one_key_kernel, dim3(B * H), dim3(64), 0, ST(stream), a);
-        GAOT_CHECK_LAUNCH("gaot_attention_fwd");
-        return GAOT_OK;
-    }
-    if (head_dim > 128) {        // 128 < head_dim <= 256: fp32 MFMA with the head dimension split over the waves (attention_wide.hip)
-        attn_wide_fwd_launch(a, false, ST(stream));
-        GAOT_CHECK_LAUNCH("gaot_attention_fwd");
-        return GAOT_OK;
-    }
-    dim3 grid(cdiv(S, 128) * B * H), block(256);
-    if (workspace != nullptr && f16 && a.vec && aligned16(workspace) && aligned16(o) && ldo % 4 == 0 && fwd_key_split_shape(B, S, H, head_dim)) {
-        a.o_part = workspace;
-        a.lse_part = workspace + 2 * (int64_t)B * S * H * head_dim;
-        const dim3 g2(cdiv(S, 256) * B * H * 2);
-        if (head_dim == 32) hipLaunchKernelGGL((attn_fwd_split_kernel<8, 32, 2, 2, true, 2>), g2, dim3(512), 0, ST(stream), a);
-        else                hipLaunchKernelGGL((attn_fwd_split_kernel<8, 64, 2, 2, true, 2>), g2, dim3(512), 0, ST(stream), a);
-        hipLaunchKernelGGL(attn_fwd_combine_kernel, dim3(cap_blocks((long)B * S * H * (head_dim / 4), 256, 2048)), dim3(256), 0, ST(stream), a);
-        GAOT_CHECK_LAUNCH("gaot_attention_fwd_ws");
-        return GAOT_OK;
-    }
-    // 256-query workgroups once they still fill the chip (one per CU): half the K / V tile splits per head
-    if (head_dim == 32 && a.vec && g_attn_split && g_attn_split != 3 && (g_attn_split == 2 || (long)cdiv(S, 256) * B * H >= 256)) {
-        if (f16) hipLaunchKernelGGL((attn_fwd_split_kernel<8, 32, 2, 2, true>), dim3(cdiv(S, 256) * B * H), dim3(512), 0, ST(stream), a);
-        else if (S % 64 == 0 && g_attn_pipe) hipLaunchKernelGGL(attn_fwd_split_pipe_kernel<0>, dim3(cdiv(S, 256) * B * H), dim3(512), 0, ST(stream), a);
-        else if (g_attn_pp / 10 == 3) hipLaunchKernelGGL((attn_fwd_split_kernel<8, 32, 3>), dim3(cdiv(S, 256) * B * H), dim3(512), 0, ST(stream), a);
-        else if (g_attn_op == 3) hipLaunchKernelGGL((attn_fwd_split_kernel<8, 32, 2>), dim3(cdiv(S, 256) * B * H), dim3(512), 0, ST(stream), a);
-        else hipLaunchKernelGGL((attn_fwd_split_kernel<8, 32, 2, 2>), dim3(cdiv(S, 256) * B * H), dim3(512), 0, ST(stream), a);
-    }
-    else if (head_dim == 32 && a.vec && g_attn_split) {
-        if (f16) hipLaunchKernelGGL((attn_fwd_split_kernel<4, 32, 2, 2, true>), grid, block, 0, ST(stream), a);
-        else if (g_attn_pp / 10 == 3) hipLaunchKernelGGL((attn_fwd_split_kernel<4, 32, 3>), grid, block, 0, ST(stream), a);
-        else if (g_attn_op == 3) hipLaunchKernelGGL((attn_fwd_split_kernel<4, 32, 2>), grid, block, 0, ST(stream), a);
-        else hipLaunchKernelGGL((attn_fwd_split_kernel<4, 32, 2, 2>), grid, block, 0, ST(stream), a);
-    }
-    else if (head_dim > 32 && head_dim <= 64 && a.vec && g_attn_split) {      // (a.vec: head_dim % 4 == 0): split-bf16 with four d steps
-        const bool two64 = g_attn_pp / 10 == 2 && g_attn_op == 2;             // two rounded pieces of everything, or exact splits
-        if (f16 && g_attn_split != 3 && (g_attn_split == 2 || (long)cdiv(S, 256) * B * H >= 256))
-            hipLaunchKernelGGL((attn_fwd_split_kernel<8, 64, 2, 2, true>), dim3(cdiv(S, 256) * B * H), dim3(512), 0, ST(stream), a);
-        else if (f16) hipLaunchKernelGGL((attn_fwd_split_kernel<4, 64, 2, 2, true>), grid, block, 0, ST(stream), a);
-        else if (g_attn_split != 3 && (g_attn_split == 2 || (long)cdiv(S, 256) * B * H >= 256))
-            { if (two64) hipLaunchKernelGGL((attn_fwd_split_kernel<8, 64, 2, 2>), dim3(cdiv(S, 256) * B * H), dim3(512), 0, ST(stream), a);
-              else hipLaunchKernelGGL((attn_fwd_split_kernel<8, 64>), dim3(cdiv(S, 256) * B * H), dim3(512), 0, ST(stream), a); }
-        else if (two64) hipLaunchKernelGGL((attn_fwd_split_kernel<4, 64, 2, 2>), grid, block, 0, ST(stream), a);
-        else hipLaunchKernelGGL((attn_fwd_split_kernel<4, 64>), grid, block, 0, ST(stream), a);
-    }
-    else if (head_dim == 32 && a.vec) hipLaunchKernelGGL(attn_fwd_glds_kernel, grid, block, 0, ST(stream), a);
-    else if (head_dim <= 32) hipLaunchKernelGGL(attn_fwd_kernel<32>, grid, block, 0, ST(stream), a);
-    else if (head_dim <= 64) hipLaunchKernelGGL(attn_fwd_kernel<64>, grid, block, 0, ST(stream), a);
-    else                     hipLaunchKernelGGL(attn_fwd_kernel<128>, grid, block, 0, ST(stream), a);      // 64 < head_dim <= 128: fp32 MFMA, one wave per SIMD
-    GAOT_CHECK_LAUNCH("gaot_attention_fwd");
-    return GAOT_OK;
+    return attention_forward(a, gather_facts(a, AttnDir::Forward, false, pieces, workspace), workspace, "gaot_attention_fwd", stream);
+}
+extern "C" int gaot_attention_fwd(const float* q, const float* k, const float* v, int64_t ldq, int64_t ldk, int64_t ldv,
+                                  int32_t B, int32_t S, int32_t H, int32_t Hkv, int32_t head_dim, float* o, int64_t ldo,
+                                  float* lse, int32_t pieces, const float* qkv_absmax, gaot_stream_t stream) {
+    return gaot_attention_fwd_ws(q, k, v, ldq, ldk, ldv, B, S, H, Hkv, head_dim, o, ldo, lse, pieces, qkv_absmax, nullptr, stream);
 }
 
 // ---- attention dropout: seed bookkeeping on the device (graph-replay safe: nothing about the seed is a launch argument)
@@ -2985,36 +3095,15 @@ extern "C" int gaot_attention_seed_next(uint64_t* state, uint64_t salt, uint64_t
     return GAOT_OK;
 }
 
-static int fill_dropout(AttnArgs& a, float p_drop, const uint64_t* seed) {
-    GAOT_REQUIRE(p_drop > 0.f && p_drop < 1.f && seed, "attention dropout: need 0 < p < 1 and a device seed word");
-    a.drop_seed = reinterpret_cast<const unsigned long long*>(seed);
-    const double keep = 1.0 - (double)p_drop;
-    a.drop_thresh = (unsigned)(keep * 4294967296.0 >= 4294967295.0 ? 4294967295.0 : keep * 4294967296.0);
-    a.drop_scale = (float)(1.0 / keep);
-    return GAOT_OK;
-}
-
 extern "C" int gaot_attention_fwd_dropout(const float* q, const float* k, const float* v, int64_t ldq, int64_t ldk, int64_t ldv,
                                           int32_t B, int32_t S, int32_t H, int32_t Hkv, int32_t head_dim, float* o, int64_t ldo,
                                           float* lse, float p_drop, const uint64_t* seed, gaot_stream_t stream) {
-    GAOT_REQUIRE(q && k && v && o && lse, "attention_fwd_dropout: null pointer");
-    GAOT_REQUIRE(B > 0 && S > 0 && H > 0 && Hkv > 0 && H % Hkv == 0, "attention_fwd_dropout: bad sizes B=%d S=%d H=%d Hkv=%d", B, S, H, Hkv);
-    GAOT_REQUIRE(head_dim > 0 && head_dim <= 256, "attention_fwd_dropout: head_dim %d not in 1..256", head_dim);
+    if (int rc = validate(ENTRY_FWD_DROPOUT, q && k && v && o && lse, 0, B, S, H, Hkv, head_dim)) return rc;
     AttnArgs a = {};
     fill_common(a, q, k, v, ldq, ldk, ldv, B, S, H, Hkv, head_dim);
     a.o = o; a.ldo = ldo; a.lse = lse;
     if (int rc = fill_dropout(a, p_drop, seed)) return rc;
-    if (head_dim > 128) {
-        attn_wide_fwd_launch(a, true, ST(stream));
-        GAOT_CHECK_LAUNCH("gaot_attention_fwd_dropout");
-        return GAOT_OK;
-    }
-    dim3 grid(cdiv(S, 128) * B * H), block(256);
-    if (head_dim <= 32)      hipLaunchKernelGGL((attn_fwd_kernel<32, true>), grid, block, 0, ST(stream), a);
-    else if (head_dim <= 64) hipLaunchKernelGGL((attn_fwd_kernel<64, true>), grid, block, 0, ST(stream), a);
-    else                     hipLaunchKernelGGL((attn_fwd_kernel<128, true>), grid, block, 0, ST(stream), a);
-    GAOT_CHECK_LAUNCH("gaot_attention_fwd_dropout");
-    return GAOT_OK;
+    return attention_forward(a, gather_facts(a, AttnDir::Forward, true, 0, nullptr), nullptr, "gaot_attention_fwd_dropout", stream);
 }
 
 extern "C" int gaot_attention_bwd_dropout(const float* q, const float* k, const float* v, int64_t ldq, int64_t ldk, int64_t ldv,
@@ -3022,57 +3111,12 @@ extern "C" int gaot_attention_bwd_dropout(const float* q, const float* k, const 
                                           int32_t H, int32_t Hkv, int32_t head_dim, float* dq, float* dk, float* dv, int64_t lddq,
                                           int64_t lddk, int64_t lddv, float* workspace, float p_drop, const uint64_t* seed,
                                           gaot_stream_t stream) {
-    GAOT_REQUIRE(q && k && v && o && dout && lse && dq && dk && dv && workspace, "attention_bwd_dropout: null pointer");
-    GAOT_REQUIRE(B > 0 && S > 0 && H > 0 && Hkv > 0 && H % Hkv == 0, "attention_bwd_dropout: bad sizes");
-    GAOT_REQUIRE(head_dim > 0 && head_dim <= 256, "attention_bwd_dropout: head_dim %d not in 1..256", head_dim);
+    if (int rc = validate(ENTRY_BWD_DROPOUT, q && k && v && o && dout && lse && dq && dk && dv && workspace, 0, B, S, H, Hkv, head_dim)) return rc;
     AttnArgs a = {};
     fill_common(a, q, k, v, ldq, ldk, ldv, B, S, H, Hkv, head_dim);
-    a.vec = a.vec && (ldo % 4 == 0) && aligned16(dout);
-    a.oin = o; a.dout = dout; a.ldo = ldo; a.lse = const_cast<float*>(lse);
-    a.dq = dq; a.dk = dk; a.dv = dv; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-    a.delta = workspace;
-    a.dq_part = workspace + (int64_t)B * H * S;
-    a.n_kblocks = cdiv(S, 128);
+    fill_backward(a, o, dout, ldo, lse, dq, dk, dv, lddq, lddk, lddv);
     if (int rc = fill_dropout(a, p_drop, seed)) return rc;
-    const int DP = head_dim <= 32 ? 32 : (head_dim <= 64 ? 64 : 128);
-    hipLaunchKernelGGL(attn_delta_kernel, dim3(cdiv((long)B * S * H, 256)), dim3(256), 0, ST(stream), a);
-    if (head_dim > 128) {        // two passes (dK / dV, then dQ): no dQ partials, no reduce
-        attn_wide_bwd_launch(a, true, ST(stream));
-        GAOT_CHECK_LAUNCH("gaot_attention_bwd_dropout");
-        return GAOT_OK;
-    }
-    dim3 grid(a.n_kblocks * B * H), block(256);
-    if (DP == 32) {
-        hipLaunchKernelGGL((attn_bwd_kernel<32, true>), grid, block, bwd_lds_bytes<32>(), ST(stream), a);
-    } else if (DP == 128) {
-        static bool attr_set128 = false;
-        if (!attr_set128) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<128, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)bwd_lds_bytes<128>());
-            attr_set128 = true;
-        }
-        hipLaunchKernelGGL((attn_bwd_kernel<128, true>), grid, block, bwd_lds_bytes<128>(), ST(stream), a);
-    } else {
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<64, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)bwd_lds_bytes<64>());
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((attn_bwd_kernel<64, true>), grid, block, bwd_lds_bytes<64>(), ST(stream), a);
-    }
-    const long total = (long)B * H * S * DP;
-    int nb = cdiv(total, 256); if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(attn_dq_reduce_kernel, dim3(nb), dim3(256), 0, ST(stream), a, DP);
-    GAOT_CHECK_LAUNCH("gaot_attention_bwd_dropout");
-    return GAOT_OK;
-}
-
-extern "C" int64_t gaot_attention_bwd_workspace(int32_t B, int32_t S, int32_t H, int32_t head_dim) {
-    if (head_dim > 128) return (int64_t)B * H * S;      // 128 < head_dim <= 256: delta only (the dQ pass writes dQ itself)
-    const int DP = head_dim <= 32 ? 32 : (head_dim <= 64 ? 64 : 128);
-    const int64_t nkb = cdiv(S, 128);
-    return (int64_t)B * H * S + nkb * B * H * S * DP;   // delta + dQ partials per key block
+    return attention_backward(a, gather_facts(a, AttnDir::Backward, true, 0, workspace), workspace, "gaot_attention_bwd_dropout", stream);
 }
 
 extern "C" int gaot_attention_bwd(const float* q, const float* k, const float* v, int64_t ldq, int64_t ldk, int64_t ldv,
@@ -3080,141 +3124,48 @@ extern "C" int gaot_attention_bwd(const float* q, const float* k, const float* v
                                   int32_t H, int32_t Hkv, int32_t head_dim, float* dq, float* dk, float* dv, int64_t lddq,
                                   int64_t lddk, int64_t lddv, float* workspace, int32_t pieces, const float* qkv_absmax,
                                   const float* dout_absmax, float* dqkv_absmax, gaot_stream_t stream) {
-    GAOT_REQUIRE(q && k && v && o && dout && lse && dq && dk && dv && workspace, "attention_bwd: null pointer");
-    GAOT_REQUIRE(pieces == 0 || (pieces >= 2 && pieces <= 4), "attention_bwd: pieces %d not in {0, 2, 3, 4}", pieces);
-    const bool f16 = pieces == 4 && qkv_absmax != nullptr && dout_absmax != nullptr && ::g_attn_pp < 0 && ::g_attn_op < 0;
-    const int g_attn_pp = ::g_attn_pp >= 0 ? ::g_attn_pp : (pieces == 2 ? 22 : 33);
-    const int g_attn_op = ::g_attn_op >= 0 ? ::g_attn_op : (pieces == 2 ? 2 : 3);
-    GAOT_REQUIRE(B > 0 && S > 0 && H > 0 && Hkv > 0 && H % Hkv == 0, "attention_bwd: bad sizes");
-    GAOT_REQUIRE(head_dim > 0 && head_dim <= 256, "attention_bwd: head_dim %d not in 1..256", head_dim);
+    if (int rc = validate(ENTRY_BWD, q && k && v && o && dout && lse && dq && dk && dv && workspace, pieces, B, S, H, Hkv, head_dim)) return rc;
     AttnArgs a = {};
     fill_common(a, q, k, v, ldq, ldk, ldv, B, S, H, Hkv, head_dim);
-    a.vec = a.vec && (ldo % 4 == 0) && aligned16(dout);
-    a.oin = o; a.dout = dout; a.ldo = ldo; a.lse = const_cast<float*>(lse);
-    a.dq = dq; a.dk = dk; a.dv = dv; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
-    a.delta = workspace;
-    a.dq_part = workspace + (int64_t)B * H * S;
-    a.n_kblocks = cdiv(S, 128);
+    fill_backward(a, o, dout, ldo, lse, dq, dk, dv, lddq, lddk, lddv);
     a.qkv_amax = qkv_absmax; a.dout_amax = dout_absmax; a.dqkv_amax = dqkv_absmax;
-    bool dkdv_published = false;
-    if (head_dim > 128) {        // 128 < head_dim <= 256 (attention_wide.hip): delta, the dK / dV pass, the dQ pass
-        if (a.vec && aligned16(o)) hipLaunchKernelGGL(attn_delta_vec_kernel, dim3(cdiv((long)B * S * H * 8, 256)), dim3(256), 0, ST(stream), a, 8);
-        else                       hipLaunchKernelGGL(attn_delta_kernel, dim3(cdiv((long)B * S * H, 256)), dim3(256), 0, ST(stream), a);
-        attn_wide_bwd_launch(a, false, ST(stream));
-        GAOT_CHECK_LAUNCH("gaot_attention_bwd");
-        if (dqkv_absmax) {       // these kernels publish nothing: one grouped-absmax launch over dQ, dK and dV
-            gaot_absmax_item it[3] = {{dq, lddq, B * S, H * head_dim, dqkv_absmax}, {dk, lddk, B * S, H * head_dim, dqkv_absmax},
-                                      {dv, lddv, B * S, H * head_dim, dqkv_absmax}};
-            if (int rc = gaot_absmax_grouped(it, 3, stream)) return rc;
-        }
-        return GAOT_OK;
-    }
-    const int DP = head_dim <= 32 ? 32 : (head_dim <= 64 ? 64 : 128);
-    const bool split_ok = head_dim == 32 && a.vec && g_attn_split && aligned16(dq) && aligned16(dk) && aligned16(dv);
-    // 128 .. 255 workgroups of 256 keys: the query tiles of a key block go to two workgroups (attn_bwd_split8_kernel QS = 2)
-    const long wg8 = (long)cdiv(S, 256) * B * H;
-    const bool qsplit = f16 && split_ok && aligned16(o) && lddk % 4 == 0 && lddv % 4 == 0 && aligned16(a.dq_part) && g_attn_split == 1 && g_attn_qsplit && wg8 >= 128 && wg8 < 256 && cdiv(S, 32) >= 8 && cdiv(S, 128) - cdiv(S, 256) >= 2;          // (two spare dQ slabs for the second half's dK / dV)
-    const bool fused_delta = f16 && split_ok && aligned16(o) && g_attn_split != 3 && (g_attn_split == 2 || wg8 >= 256 || qsplit);   // the fp16 8-wave kernel forms delta itself
-    if (fused_delta) {
-    } else if (a.vec && aligned16(o)) {
-        const int lpr = 8;
-        hipLaunchKernelGGL(attn_delta_vec_kernel, dim3(cdiv((long)B * S * H * lpr, 256)), dim3(256), 0, ST(stream), a, lpr);
-    } else {
-        hipLaunchKernelGGL(attn_delta_kernel, dim3(cdiv((long)B * S * H, 256)), dim3(256), 0, ST(stream), a);
-    }
-    dim3 grid(a.n_kblocks * B * H), block(256);
-    if (qsplit) {
-        a.n_kblocks = cdiv(S, 256);
-        a.dk2 = a.dq_part + (long)a.n_kblocks * B * H * S * 32;          // the first two slabs the 256-key blocks leave unused
-        a.dv2 = a.dk2 + (long)B * H * S * 32;
-        // (attn_bwd_h16_kernel<8, 2> measured equal here -- 76.5 against 77.2 us at 4 x 1 024 tokens: sixteen query tiles per workgroup -- so this
-        // shape stays on the kernel its tests were written against)
-        hipLaunchKernelGGL((attn_bwd_split8_kernel<2, 2, true, true, 2>), dim3(a.n_kblocks * B * H * 2), dim3(512), 0, ST(stream), a);
-        {
-            const long rows = (long)B * S;
-            const int c4 = H * 32 / 4;
-            hipLaunchKernelGGL(attn_add_cols_kernel, dim3(cap_blocks(rows * c4, 256, 2048)), dim3(256), 0, ST(stream), dk, (long)lddk, a.dk2, dv, (long)lddv, a.dv2, rows, c4);
-        }
-        dkdv_published = true;
-    } else if (split_ok && g_attn_split != 3 && (g_attn_split == 2 || (long)cdiv(S, 256) * B * H >= 256)) {
-        a.n_kblocks = cdiv(S, 256);          // 256 keys per workgroup: half the dQ slabs (the workspace is sized for 128)
-        if (f16 && fused_delta && g_attn_h16 == 4 && (long)B * H * S >= 1024) { a.n_kblocks = cdiv(S, 128); hipLaunchKernelGGL((attn_bwd_h16_kernel<4>), dim3(a.n_kblocks * B * H), dim3(256), 0, ST(stream), a); dkdv_published = true; }
-        else if (f16 && fused_delta && (g_attn_h16 & 15) == 8 && (long)B * H * S >= 1024) {
-            const dim3 g8(a.n_kblocks * B * H);
-            switch (g_attn_h16 >> 4) {
-                case 1: hipLaunchKernelGGL((attn_bwd_h16_kernel<8, 1, 1>), g8, dim3(512), 0, ST(stream), a); break;
-                case 2: hipLaunchKernelGGL((attn_bwd_h16_kernel<8, 1, 2>), g8, dim3(512), 0, ST(stream), a); break;
-                case 3: hipLaunchKernelGGL((attn_bwd_h16_kernel<8, 1, 3>), g8, dim3(512), 0, ST(stream), a); break;
-                default: hipLaunchKernelGGL((attn_bwd_h16_kernel<8>), g8, dim3(512), 0, ST(stream), a); break;
-            }
-            dkdv_published = true;
-        }
-        else if (f16 && fused_delta) { hipLaunchKernelGGL((attn_bwd_split8_kernel<2, 2, true, true>), dim3(a.n_kblocks * B * H), dim3(512), 0, ST(stream), a); dkdv_published = true; }
-        else if (g_attn_pp % 10 == 3) hipLaunchKernelGGL(attn_bwd_split8_kernel<3>, dim3(a.n_kblocks * B * H), dim3(512), 0, ST(stream), a);
-        else if (g_attn_op == 3) hipLaunchKernelGGL(attn_bwd_split8_kernel<2>, dim3(a.n_kblocks * B * H), dim3(512), 0, ST(stream), a);
-        else if (g_attn_tr) hipLaunchKernelGGL((attn_bwd_split8_kernel<2, 2, true>), dim3(a.n_kblocks * B * H), dim3(512), 0, ST(stream), a);
-        else hipLaunchKernelGGL((attn_bwd_split8_kernel<2, 2>), dim3(a.n_kblocks * B * H), dim3(512), 0, ST(stream), a);
-    } else if (split_ok) {
-        hipLaunchKernelGGL(attn_bwd_split_kernel, grid, block, 0, ST(stream), a);
-    } else if (head_dim > 32 && head_dim <= 64 && a.vec && g_attn_split && aligned16(dq) && aligned16(dk) && aligned16(dv)) {
-        const long wg8d = (long)cdiv(S, 256) * B * H;
-        // [r6] fp16 pieces on eight waves: 256-key blocks when they fill the chip, shared between two workgroups (QS = 2) at 128 .. 255 blocks
-        const bool f16_qs = f16 && g_attn_dh8 && g_attn_split != 3 && lddk % 4 == 0 && lddv % 4 == 0 && aligned16(a.dq_part) && wg8d >= 128 && wg8d < 256 && cdiv(S, 32) >= 8 && cdiv(S, 128) - cdiv(S, 256) >= 2;
-        if (f16 && g_attn_dh8 && g_attn_split != 3 && wg8d >= 256) {
-            a.n_kblocks = cdiv(S, 256);
-            hipLaunchKernelGGL((attn_bwd_split8_dh_kernel<true, 1>), dim3(a.n_kblocks * B * H), dim3(512), 0, ST(stream), a);
-            dkdv_published = true;
-        } else if (f16_qs) {
-            a.n_kblocks = cdiv(S, 256);
-            a.dk2 = a.dq_part + (long)a.n_kblocks * B * H * S * 64;          // the first two slabs the 256-key blocks leave unused
-            a.dv2 = a.dk2 + (long)B * H * S * 64;
-            hipLaunchKernelGGL((attn_bwd_split8_dh_kernel<true, 2>), dim3(a.n_kblocks * B * H * 2), dim3(512), 0, ST(stream), a);
-            const long rows = (long)B * S;
-            const int c4 = H * head_dim / 4;
-            hipLaunchKernelGGL(attn_add_cols_kernel, dim3(cap_blocks(rows * c4, 256, 2048)), dim3(256), 0, ST(stream), dk, (long)lddk, a.dk2, dv, (long)lddv, a.dv2, rows, c4);
-            dkdv_published = true;
-        }
-        else if (g_attn_pp % 10 == 2 && g_attn_op == 2 && g_attn_tr && g_attn_split != 3 && (g_attn_split == 2 || (long)cdiv(S, 256) * B * H >= 256)) {      // (C5: 128 such workgroups: stays on the 4-wave kernel, 800 vs 822 us)
-            a.n_kblocks = cdiv(S, 256);          // 256 keys per workgroup: half the dQ slabs (the workspace is sized for 128)
-            hipLaunchKernelGGL((attn_bwd_split8_dh_kernel<false, 1>), dim3(a.n_kblocks * B * H), dim3(512), 0, ST(stream), a);
-        }
-        else if (f16) hipLaunchKernelGGL((attn_bwd_split_dh_kernel<64, 2, 2, true>), grid, block, 0, ST(stream), a);
-        else if (g_attn_pp % 10 == 2 && g_attn_op == 2) hipLaunchKernelGGL((attn_bwd_split_dh_kernel<64, 2, 2>), grid, block, 0, ST(stream), a);
-        else hipLaunchKernelGGL((attn_bwd_split_dh_kernel<64>), grid, block, 0, ST(stream), a);
-    } else if (DP == 32) {
-        hipLaunchKernelGGL(attn_bwd_kernel<32>, grid, block, bwd_lds_bytes<32>(), ST(stream), a);
-    } else if (DP == 64) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)bwd_lds_bytes<64>());
-            attr_set = true;
-        }
-        hipLaunchKernelGGL(attn_bwd_kernel<64>, grid, block, bwd_lds_bytes<64>(), ST(stream), a);
-    } else {
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)bwd_lds_bytes<128>());
-            attr_set = true;
-        }
-        hipLaunchKernelGGL(attn_bwd_kernel<128>, grid, block, bwd_lds_bytes<128>(), ST(stream), a);
-    }
-    const long total = (long)B * H * S * DP;
-    int nb = cdiv(total, 256); if (nb > 4096) nb = 4096;
-    const bool vec_ok = head_dim % 4 == 0 && aligned16(dq) && lddq % 4 == 0 && aligned16(a.dq_part) && total < (1L << 31);
-    if (vec_ok && DP == 32 && head_dim == 32)
-        hipLaunchKernelGGL(attn_dq_reduce_vec_kernel<8>, dim3(cap_blocks(total / 4, 256, 1024)), dim3(256), 0, ST(stream), a);
-    else if (vec_ok && DP == 64)
-        hipLaunchKernelGGL(attn_dq_reduce_vec_kernel<16>, dim3(cap_blocks(total / 4, 256, 2048)), dim3(256), 0, ST(stream), a);
-    else if (vec_ok && DP == 128)
-        hipLaunchKernelGGL(attn_dq_reduce_vec_kernel<32>, dim3(cap_blocks(total / 4, 256, 2048)), dim3(256), 0, ST(stream), a);
-    else
-        hipLaunchKernelGGL(attn_dq_reduce_kernel, dim3(nb), dim3(256), 0, ST(stream), a, DP);
-    GAOT_CHECK_LAUNCH("gaot_attention_bwd");
-    if (dqkv_absmax && !dkdv_published) {        // main kernels that do not publish: one grouped-absmax launch over dK and dV
-        gaot_absmax_item it[2] = {{dk, lddk, B * S, H * head_dim, dqkv_absmax}, {dv, lddv, B * S, H * head_dim, dqkv_absmax}};
-        if (int rc = gaot_absmax_grouped(it, 2, stream)) return rc;
-    }
+    return attention_backward(a, gather_facts(a, AttnDir::Backward, false, pieces, workspace), workspace, "gaot_attention_bwd", stream);
+}
+
+// ---- the plan as numbers (include/gaot_hip_debug.h lists the columns)
+static void plan_columns(const AttnPlan& p, int64_t out[GAOT_ATTENTION_PLAN_COLUMNS]) {
+    const int64_t cols[GAOT_ATTENTION_PLAN_COLUMNS] = {
+        (int)p.delta, p.delta_grid, (int)p.family, p.nw, p.dh, p.pp, p.op, p.f16, p.ks, p.tr, p.qs, p.var, p.drop, p.grid, p.block, p.lds_bytes,
+        p.keys_per_wg, p.n_kblocks, p.combine_grid, p.add_cols_grid, (int)p.reduce, p.reduce_dp4, p.reduce_grid, p.absmax_tensors,
+        p.o_part, p.lse_part, p.delta_off, p.dq_part, p.dk2, p.dv2, p.workspace_floats};
+    for (int i = 0; i < GAOT_ATTENTION_PLAN_COLUMNS; ++i) out[i] = cols[i];
+}
+
+extern "C" int gaot_debug_attention_plan(const gaot_debug_attention_query* c, int64_t out[GAOT_ATTENTION_PLAN_COLUMNS]) {
+    GAOT_REQUIRE(c != nullptr && out != nullptr, "attention_plan: null pointer");
+    GAOT_REQUIRE((c->direction == 0 || c->direction == 1) && (c->dropout == 0 || c->dropout == 1), "attention_plan: direction %d, dropout %d not 0 / 1", c->direction, c->dropout);
+    const bool fwd = c->direction == 0, dropout = c->dropout != 0;
+    if (int rc = validate((AttnEntry)(2 * c->direction + c->dropout), true, c->pieces, c->B, c->S, c->H, c->Hkv, c->head_dim)) return rc;
+    auto bit = [&](uint32_t b) { return (c->facts & b) != 0; };
+    AttnFacts f = {};
+    f.B = c->B; f.S = c->S; f.H = c->H; f.Hkv = c->Hkv; f.D = c->head_dim;
+    f.dir = fwd ? AttnDir::Forward : AttnDir::Backward; f.dropout = dropout; f.pieces = dropout ? 0 : c->pieces;
+    f.has_qkv_absmax = !dropout && bit(GAOT_ATTN_FACT_QKV_ABSMAX);
+    f.has_dout_absmax = !dropout && !fwd && bit(GAOT_ATTN_FACT_DOUT_ABSMAX);
+    f.has_dqkv_absmax = !dropout && !fwd && bit(GAOT_ATTN_FACT_DQKV_ABSMAX);
+    f.vec = c->head_dim % 4 == 0 && bit(GAOT_ATTN_FACT_VEC);
+    f.o_aligned = bit(GAOT_ATTN_FACT_O_ALIGNED); f.ldo4 = bit(GAOT_ATTN_FACT_LDO4);
+    f.has_workspace = (!fwd || !dropout) && bit(GAOT_ATTN_FACT_WORKSPACE); f.ws_aligned = bit(GAOT_ATTN_FACT_WS_ALIGNED);
+    f.dq_aligned = bit(GAOT_ATTN_FACT_DQ_ALIGNED); f.dk_aligned = bit(GAOT_ATTN_FACT_DK_ALIGNED); f.dv_aligned = bit(GAOT_ATTN_FACT_DV_ALIGNED);
+    f.lddq4 = bit(GAOT_ATTN_FACT_LDDQ4); f.lddk4 = bit(GAOT_ATTN_FACT_LDDK4); f.lddv4 = bit(GAOT_ATTN_FACT_LDDV4);
+    f.dq_part_aligned = bit(GAOT_ATTN_FACT_DQ_PART_ALIGNED);
+    plan_columns(plan_attention(f, g_sw), out);
+    return GAOT_OK;
+}
+
+extern "C" int gaot_debug_last_attention_plan(int direction, int64_t out[GAOT_ATTENTION_PLAN_COLUMNS]) {
+    GAOT_REQUIRE(out != nullptr && (direction == 0 || direction == 1), "last_attention_plan: null output or direction %d not 0 / 1", direction);
+    if (t_has_plan[direction]) plan_columns(t_last_plan[direction], out);
+    else for (int i = 0; i < GAOT_ATTENTION_PLAN_COLUMNS; ++i) out[i] = -1;      // no launch on this thread yet
     return GAOT_OK;
 }

@@ -81,6 +81,43 @@ int gaot_debug_set_attention_tr(int on);
 /* tuning hook: 1 = the software-pipelined 8-wave split forward where it applies (S % 64 == 0), 0 (default) = the plain one.
  * Returns the previous value. */
 int gaot_debug_set_attention_pipe(int on);
+/* which kernels an attention call WOULD run, under the switches as they stand (csrc/attention_plan.h; launches nothing and touches no
+ * memory).  The call is described by its sizes, `pieces`, direction (0 forward: gaot_attention_fwd_ws, 1 backward: gaot_attention_bwd),
+ * dropout (1: the _dropout entry of that direction; pieces and the absmax bits are then ignored) and the facts the entry point reads off
+ * its pointers and pitches, as bits:
+ *   QKV_ABSMAX, DOUT_ABSMAX, DQKV_ABSMAX  that pointer given
+ *   VEC              q, k, v 16-byte aligned, their pitches % 4 == 0; backward: dout and ldo too (head_dim % 4 is read off head_dim)
+ *   O_ALIGNED        o 16-byte aligned                       LDO4  ldo % 4 == 0 (forward)
+ *   WORKSPACE        forward: a workspace given              WS_ALIGNED  ... and 16-byte aligned
+ *   DQ_ / DK_ / DV_ALIGNED, LDDQ4 / LDDK4 / LDDV4            the backward's outputs and their pitches % 4 == 0
+ *   DQ_PART_ALIGNED  workspace + B H S floats 16-byte aligned (backward)
+ * out = {0 delta step (0 none: forward or fused, 1 vector, 2 scalar), 1 its grid,
+ *        2 family of the main kernel (0 one key, 1 wide (attention_wide.hip), 2 fp32 MFMA attn_fwd_kernel / attn_bwd_kernel<dh, drop>, 3
+ *          attn_fwd_glds_kernel, 4 attn_fwd_split_kernel<nw, dh, pp, op, f16, ks>, 5 attn_fwd_split_pipe_kernel, 6 attn_bwd_split_kernel,
+ *          7 attn_bwd_split_dh_kernel<dh, pp, op, f16>, 8 attn_bwd_split8_kernel<pp, op, tr, f16, qs>, 9 attn_bwd_h16_kernel<nw, qs, var>,
+ *          10 attn_bwd_split8_dh_kernel<f16, qs>),
+ *        3 nw, 4 dh, 5 pp, 6 op, 7 f16, 8 ks, 9 tr, 10 qs, 11 var, 12 drop  (template arguments of that family; the others 0),
+ *        13 grid, 14 block, 15 dynamic LDS bytes, 16 keys (forward: queries) per workgroup, 17 n_kblocks (dQ slabs written),
+ *        18 grid of the key-split combine (0 none), 19 grid of the query-split add_cols launch (0 none),
+ *        20 dQ reduce (0 none, 1 vector, 2 scalar), 21 its DP4 (8 / 16 / 32), 22 its grid,
+ *        23 tensors under the trailing grouped absmax (0, 2: dK dV, 3: dQ dK dV),
+ *        24 o_part, 25 lse_part, 26 delta, 27 dq_part, 28 dk2, 29 dv2  (floats from the workspace base; -1 unused),
+ *        30 workspace floats the caller must provide};  GAOT_OK, or the error the entry point gives for those sizes */
+typedef struct gaot_debug_attention_query {
+    int32_t B, S, H, Hkv, head_dim, pieces, direction, dropout;
+    uint32_t facts;
+} gaot_debug_attention_query;
+enum {
+    GAOT_ATTN_FACT_QKV_ABSMAX = 1 << 0, GAOT_ATTN_FACT_DOUT_ABSMAX = 1 << 1, GAOT_ATTN_FACT_DQKV_ABSMAX = 1 << 2, GAOT_ATTN_FACT_VEC = 1 << 3,
+    GAOT_ATTN_FACT_O_ALIGNED = 1 << 4, GAOT_ATTN_FACT_LDO4 = 1 << 5, GAOT_ATTN_FACT_WORKSPACE = 1 << 6, GAOT_ATTN_FACT_WS_ALIGNED = 1 << 7,
+    GAOT_ATTN_FACT_DQ_ALIGNED = 1 << 8, GAOT_ATTN_FACT_DK_ALIGNED = 1 << 9, GAOT_ATTN_FACT_DV_ALIGNED = 1 << 10,
+    GAOT_ATTN_FACT_LDDQ4 = 1 << 11, GAOT_ATTN_FACT_LDDK4 = 1 << 12, GAOT_ATTN_FACT_LDDV4 = 1 << 13, GAOT_ATTN_FACT_DQ_PART_ALIGNED = 1 << 14
+};
+#define GAOT_ATTENTION_PLAN_COLUMNS 31
+int gaot_debug_attention_plan(const gaot_debug_attention_query* call, int64_t out[GAOT_ATTENTION_PLAN_COLUMNS]);
+/* the plan the calling thread's last forward (direction 0) or backward (1) attention launch executed, dropout entries included: the same
+ * columns; all -1 before the first such launch.  A call that fails its checks leaves it as it was. */
+int gaot_debug_last_attention_plan(int direction, int64_t out[GAOT_ATTENTION_PLAN_COLUMNS]);
 /* tuning hook (results become WRONG): forward kernel 1 = no stores, 2 = no GELU, 4 = no MFMA layers, 8 = no weight staging */
 int gaot_debug_set_kernel_mlp_ablate(int bits);
 /* A/B hook: 1 (default) = the bf16-split kernel-MLP kernels (fp32-level products on v_mfma_f32_32x32x16_bf16), 0 = the fp32-MFMA

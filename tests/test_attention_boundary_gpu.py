@@ -6,7 +6,9 @@ A. `_call` drives gaot_attention_fwd_ws / _bwd (and the two _dropout entries, wi
    sentinel before the call; after it everything outside the output regions is bit-identical to what it was (inputs included), every
    output element is finite and no longer the sentinel, and o, lse, dq, dk, dv match float64 tensor by tensor.
 
-   Alignment guards, read in gaot_attention_fwd_ws / gaot_attention_bwd and the kernels they launch before the first run:
+   Alignment guards, read in gaot_attention_fwd_ws / gaot_attention_bwd and the kernels they launch before the first run (each is now
+   a boolean of AttnFacts in csrc/attention_plan.h -- vec, o_aligned, ldo4, ws_aligned, dq_ / dk_ / dv_aligned, lddq4 / lddk4 / lddv4,
+   dq_part_aligned -- gathered in one place, attention.hip gather_facts, and read by plan_attention):
      * q / k / v loads: 16-byte loads only behind AttnArgs.vec (head_dim, ldq, ldk, ldv multiples of 4, q, k, v 16-byte aligned); the
        backward adds ldo % 4 and aligned16(dout) to it (the 16-byte dO loads).                                             guarded
      * stores to o (every forward kernel), to dk / dv (every backward kernel), to dq of the wide kernels: scalar.          guarded
